@@ -24,7 +24,18 @@ Sharding over N GPUs:
                      ranks; partial blur sum + boundary subframes are exchanged before the backward, gradients are
                      summed after it.  value = K * steps / seconds.
 
-Prints ONE JSON line on rank 0 (metric contract + "roofline" for the dominant kernel + "cpu_baseline").
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps in one region and prints the
+metric contract (value, ms_per_step = the milliseconds of one timed step, ...) and nothing that needs work of its own.
+--full adds everything else this file measures, each with runs of its own: the headline as the median of three regions
+of --steps steps, the per-stage timings with "roofline" and "pipeline_hbm", the regions with depth images and on the
+reference's lists, forward-only inference, "cpu_baseline", and for N > 1 the other sharding modes, the all-reduce A/B
+and RCCL's own log.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed in its last step, DIR/<name>.npy in
+float32 (float64 for the losses): the parameters and Adam moments of every optimiser group, the densification statistics
+and the step's two loss values.  Per-Gaussian arrays are the rows of a fixed sample (DUMP_ROWS, seed 0, sorted; the
+indices are dump_rows.npy) so that the files stay below 64 MB; the inputs are seeded, so equal arguments give equal
+inputs and two builds can be compared file by file.
 """
 import argparse
 import json
@@ -87,6 +98,12 @@ def parse_args(argv=None):
                          "point-to-point all-reduce A/B)")
     ap.add_argument("--no-optimizer", action="store_true",
                     help="time query + loss + backward (+ all-reduce) only, without densification stats and Adam")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (three regions, stage timings, roofline, depth / "
+                         "reference-list / forward-only regions, CPU baselines; N > 1: other modes, all-reduce A/B, RCCL "
+                         "log); off: time --steps steps once and print the metric line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (see the module docstring)")
     return ap.parse_args(argv)
 
 
@@ -202,6 +219,51 @@ def stage_bytes(P, Pv_tot, R_tot, N, K, s):
         # inside this stage
         "tile_cull": (4 + 20) * P * K + 36 * Pv_tot + (0 if P * K <= (1 << 24) else 16 * P * K + 8 * P * K),
     }
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_ROWS = 65536           # per-Gaussian arrays: this many rows (all of them for a smaller cloud)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, cloud, last):
+    """What one training step hands its caller: the parameters and Adam moments of every optimiser group (the step leaves
+    the gradients set to None), the densification statistics, and `last`, the step's return (its loss values).  Arrays
+    with one row per Gaussian are cut to a fixed, seeded sample of rows.  Returns {name: bytes written}."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    P = int(cloud._xyz.shape[0])
+    rows = np.arange(P) if P <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(P, DUMP_ROWS, replace=False))
+    rows_dev = torch.from_numpy(rows).to(cloud._xyz.device)
+    arrays = {"dump_rows": rows.astype(np.float64)}
+
+    def put(name, t):
+        t = t.detach()
+        if t.dim() > 0 and t.shape[0] == P:
+            t = t.index_select(0, rows_dev)
+        arrays[name] = t.float().cpu().numpy()
+    for group in cloud.optimizer.param_groups:
+        name = group.get("name", f"group{len(arrays)}")
+        for p in group["params"]:
+            put(f"param_{name}", p)
+            state = cloud.optimizer.state.get(p, {})
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key in state:
+                    put(f"{key}_{name}", state[key])
+    for name in ("max_radii2D", "xyz_gradient_accum", "denom"):
+        put(f"stats_{name}", getattr(cloud, name))
+    for name in ("l1", "smooth"):
+        v = last.get(name) if last else None
+        if v is not None:
+            arrays[f"loss_{name}"] = np.asarray([float(v)], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.nbytes) for name, a in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------------------ CPU baselines
@@ -354,8 +416,10 @@ def run_rank(args):
                           DGS_DIST_FORCE_INIT="1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     rccl_log = None
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or emu is not None:
+    if args.full and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or emu is not None):
         rccl_log = rccl_log_setup(int(os.environ.get("RANK", "0")))
+    # the step's host draws (background colour, alignment jitter) and every other torch draw: the same inputs on every run
+    torch.manual_seed(0)
     rank, world_env, local_rank = sharding.init_distributed("cuda")
     world = dist.get_world_size() if dist.is_initialized() else 1
     if world != max(args.gpus, 1):
@@ -458,7 +522,7 @@ def run_rank(args):
 
     def step():
         stats["it"] += 1
-        loop.step(stats["it"], 0)
+        stats["last"] = loop.step(stats["it"], 0)
 
     def sync():
         if world > 1:
@@ -491,18 +555,23 @@ def run_rank(args):
     for _ in range(args.warmup):
         step()
     sync()
-    with torch.no_grad():       # measured Pv of this rank's workload (an output of the forward)
-        probe = motion.query(0, "all", compute_blurred=False, shard=shard_id if subframes_mode else None)
-        Pv_tot = int((probe["radii_all"] > 0).sum().item())
-        del probe
+    Pv_tot = None
+    if args.full:
+        with torch.no_grad():       # measured Pv of this rank's workload (an output of the forward)
+            probe = motion.query(0, "all", compute_blurred=False, shard=shard_id if subframes_mode else None)
+            Pv_tot = int((probe["radii_all"] > 0).sum().item())
+            del probe
     # (N ranks: the step up to its first collective is replayed -- FusedStep.replay_front)
     replayed_before = loop._fused.replayed if loop._fused is not None else 0
     # the timed region never carries the stage timers (their event pairs, and -- csrc/api.hip -- the compositing backward
-    # as one launch instead of parts); the per-stage durations come from a second region right after it
-    # the region is run three times back to back (one region of 20 steps is 0.2 s, and box-to-box noise is as
-    # large as a round's gain); every region is exactly args.steps steps between barriers; the headline is the MEDIAN region
-    region_dts = [timed(args.steps, profile=False) for _ in range(1 if emu is not None else 3)]
+    # as one launch instead of parts); with --full the per-stage durations come from a second region right after it
+    # --full runs the region three times back to back (one region of 20 steps is 0.2 s, and box-to-box noise is
+    # as large as a round's gain) and the headline is the MEDIAN region; every region is exactly args.steps steps between
+    # barriers
+    region_dts = [timed(args.steps, profile=False) for _ in range(3 if args.full and emu is None else 1)]
     dt = sorted(region_dts)[len(region_dts) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cloud, stats.get("last"))
     per_rank = None
     if world > 1:       # every rank's own time for the region (the headline divides by the slowest)
         mine = torch.tensor([stats["dt_local"]], dtype=torch.float64, device=dev)
@@ -523,10 +592,12 @@ def run_rank(args):
     # did the timed region replay the captured step?  (TrainingLoop(graph="auto") leaves large views to the eager fused step)
     replaying = loop._fused is not None and loop._fused.replayed > replayed_before
     if replaying:
+        graph_info = {"captured": loop._fused.captured, "replayed": loop._fused.replayed}
+    prof = None
+    if args.full and replaying:
         # The timed region replayed the captured step (one hipGraph launch per iteration): HIP events cannot be recorded
         # between the kernels of a graph, so the per-stage durations come from a second, EAGER region of the same step
         # (same kernels, same arguments) right after it.
-        graph_info = {"captured": loop._fused.captured, "replayed": loop._fused.replayed}
         loop.graph = False
         for _ in range(2):
             step()
@@ -535,12 +606,13 @@ def run_rank(args):
         stats["profiled_steps"] = n_prof
         graph_info["eager_ms_per_step"] = round(dt_eager / n_prof * 1e3, 3)
         loop.graph = True
-    else:
+    elif args.full:
         n_prof = max(10, min(args.steps, 30))
         dt_prof = timed(n_prof, profile=True)
         stats["profiled_steps"] = n_prof
         stats["profiled_ms_per_step"] = round(dt_prof / n_prof * 1e3, 3)
-    prof = _lib.profile_read()
+    if args.full:
+        prof = _lib.profile_read()
 
     # the same step on the reference's duplicate lists (tile_cull = 0: sort keys / point lists bit-identical to the
     # reference's), reported beside the headline value
@@ -664,7 +736,8 @@ def run_rank(args):
             fs.invalidate()
 
     ref_lists = with_depth = ref_lists_depth = None
-    if world == 1 and emu is None and not args.no_reference_lists and dgr.TILE_CULL and not args.autograd_path:
+    if (args.full and world == 1 and emu is None and not args.no_reference_lists and dgr.TILE_CULL and
+            not args.autograd_path):
         with_depth = side_region(True, False, "the headline step + the K depth images composited and stored "
                                               "(composite_fwd_kernel<true, true>), as every render of the reference does")
         ref_lists = side_region(False, True, "same step with DgsProblem.tile_cull = 0: the duplicate lists, sort keys and "
@@ -678,7 +751,7 @@ def run_rank(args):
     # gradient: DgsProblem.forward_only = 1 (no final_T / n_contrib / cov3D / mask stores), the exact two-phase forward
     # with its one host read per call, depth images included (render() returns them).
     fwd_only = None
-    if world == 1 and emu is None and not args.autograd_path:
+    if args.full and world == 1 and emu is None and not args.autograd_path:
         from deblurgs_amd import gaussian_renderer
         with torch.no_grad():
             wv_, fp_, cc_ = (t.contiguous() for t in motion.get_trajectory_matrices(0))
@@ -717,59 +790,12 @@ def run_rank(args):
                                               "two-phase forward with its host read; GPU-bound (about 30 small launches)"}}
 
     if rank == 0:
-        # R from a state-level forward (the operator keeps it in its autograd ctx)
-        with torch.no_grad():
-            wv, fp, cc = motion.get_trajectory_matrices(0)
-            rs = dgr.GaussianRasterizationSettings(H, W, scene["tanfovx"], scene["tanfovy"],
-                                                   torch.from_numpy(scene["bg"]).to(dev), 1.0, 0.2, 100.0, False,
-                                                   args.sh_degree, cc, False, False)
-            R_tot = dgr._forward_impl(K, cloud.get_xyz.detach(), cloud.get_features.detach().contiguous(), None,
-                                      cloud.get_opacity.detach().reshape(-1), cloud.get_scaling.detach(),
-                                      cloud.get_rotation.detach(), None, wv.contiguous(), fp.contiguous(),
-                                      cc.contiguous(), rs)[0]
         N = W * H
         s = (args.sh_degree + 1) ** 2
         frac_k = 1.0
         if subframes_mode:       # this rank's share of the K subframes
             k0, k1 = sharding.shard_range(K, shard_id[0], shard_id[1])
             frac_k = (k1 - k0) / K
-        bytes_by_stage = stage_bytes(P, Pv_tot, R_tot * frac_k, N, K * frac_k, s)
-        stages = {}
-        for name, (ms, calls) in prof.items():
-            if calls == 0:
-                continue
-            avg_ms = ms / calls
-            gbs = bytes_by_stage[name] / (avg_ms * 1e-3) / 1e9
-            # model_GBps: the byte MODEL of SURVEY 8d over the measured time -- not achieved bandwidth (for geometry_bwd the
-            # model counts the K-summed Pv reads the fused kernel does not repeat); traffic_* (below) is counter-based
-            stages[name] = {"avg_ms": round(avg_ms, 4), "launches": calls, "alg_bytes": int(bytes_by_stage[name]),
-                            "model_GBps": round(gbs, 1), "ms_per_step": round(ms / max(stats["profiled_steps"], 1), 4),
-                            "traffic_bytes": None, "traffic_GBps": None}
-            if name == "contrib_reduce":
-                moved = 48 * R_tot * frac_k + 64 * Pv_tot
-                stages[name]["moved_bytes"] = int(moved)
-                stages[name]["moved_GBps"] = round(moved / (avg_ms * 1e-3) / 1e9, 1)
-        # counter-based HBM bytes per step and stage: the committed FETCH_SIZE / WRITE_SIZE passes of this same command
-        # (profiles/traffic_rNN.json, `_per_step`; PMC counters cannot be collected from inside this process), over THIS
-        # run's stage times -- same provenance rule as roofline.traffic
-        traffic_doc, traffic_file = None, None
-        import glob as _glob
-        for path in sorted(_glob.glob(os.path.join(ROOT, "profiles", "traffic_r[0-9][0-9].json")))[::-1]:
-            try:
-                doc = json.load(open(path))
-            except Exception:
-                continue
-            if doc.get("_config") == args.config and "_per_step" in doc and world == 1 and emu is None \
-                    and args.sh_degree == doc.get("_sh_degree", 2):
-                traffic_doc, traffic_file = doc, os.path.basename(path)
-                break
-        if traffic_doc is not None:
-            for name, nbytes in traffic_doc["_per_step"].items():
-                if name in stages and stages[name]["ms_per_step"] > 0:
-                    stages[name]["traffic_bytes"] = int(nbytes)
-                    stages[name]["traffic_GBps"] = round(nbytes / (stages[name]["ms_per_step"] * 1e-3) / 1e9, 1)
-        dom = max(stages, key=lambda n: stages[n]["avg_ms"])
-        total_bytes = sum(bytes_by_stage.values())
         ms_per_step = dt / args.steps * 1e3
         value = views_per_step * K * args.steps / dt
         result = {
@@ -810,55 +836,107 @@ def run_rank(args):
                        # what the timed step renders: the K colour images; the depth images only if something reads them
                        # (the reference always composites them: see value_with_depth)
                        "depth_output": bool(loop._fused is not None and loop._fused.always_depth) or args.autograd_path,
-                       # csrc/api.hip: how many parts the timed region's compositing backward ran in (1 = one launch; > 1: a
-                       # large view enqueued eagerly, each part's row totals on a side stream beside the next part's
-                       # compositing, bit-identical -- DESIGN.md 7); the per-stage averages below are taken with the stage
-                       # timers on, i.e. with ONE launch per step
-                       # and only for eagerly enqueued steps: the library does not fork inside a stream capture (a forked
-                       # executable graph does not give its memory back on this runtime, tools/graph_fork_leak.hip)
-                       "backward_in_parts": (int(_lib.lib().dgs_backward_parts(_lib.context(), int(round(K * frac_k)), int(R_tot * frac_k),
-                                                                               int(bool(dgr.TILE_CULL)))) if
-                                             (not graph_info or _lib.context_overlap_mode() == 3) else 1),
-                       "profiled_region_ms_per_step": stats.get("profiled_ms_per_step"),
                        "sharding": (args.shard if world > 1 else "none"), "ranks_in_process_group": world,
                        "ar_chunks": (args.ar_chunks if world > 1 and loop._fused is not None else None),
                        "allreduce": (sharding.ALLREDUCE_MODE if world > 1 else None),
-                       "allreduce_ms_per_step": None if allreduce_ms is None else round(allreduce_ms, 3),
-                       "Pv_total": Pv_tot, "R_total": int(R_tot),
-                       "pixel_gaussian_evals_upper_bound_per_step": int(256 * R_tot)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": stages[dom]["model_GBps"], "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(stages[dom]["model_GBps"] / HBM_PEAK_GBS, 5), "traffic": None,
-                         "alg_bytes_per_launch": stages[dom]["alg_bytes"], "avg_launch_ms": stages[dom]["avg_ms"],
-                         "avg_launch_ms_source": "HIP events on the launch stream inside this run (dgs_profile_*)" +
-                                                 (", recorded in the eager region that follows the replayed one" if graph_info else "") +
-                                                 "; with the stage timers on the compositing backward runs as ONE launch "
-                                                 "per step (as it does inside a captured graph; an eagerly enqueued step "
-                                                 "runs it in parts, see config.backward_in_parts), and "
-                                                 "profiles/r06_kernel_stats.csv is taken the same way (DGS_BWD_OVERLAP=0)",
-                         "note": "the dominant kernel (compositing) is bound by VALU issue, not by HBM (SURVEY 8d): `frac` is "
-                                 "the honest HBM fraction of its byte model, `valu` (when the round's PMC profile of this "
-                                 "config is committed) the fraction of the VALU issue peak it reaches"},
-            "pipeline_hbm": {"alg_bytes_per_step": int(total_bytes),
-                             "model_GBps": round(total_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-                             "frac": round(total_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                             # counter-based: every kernel of the step (loss image and Adam included), committed passes
-                             "traffic_bytes_per_step": (int(traffic_doc["_per_step_total"]) if traffic_doc is not None
-                                                        else None),
-                             "traffic_GBps": (round(traffic_doc["_per_step_total"] / (ms_per_step * 1e-3) / 1e9, 1)
-                                              if traffic_doc is not None else None),
-                             "traffic_source": (f"profiles/{traffic_file}: {traffic_doc.get('_source', '')}"
-                                                if traffic_doc is not None else None)},
-            "regions": {"ms_per_step": [round(x / args.steps * 1e3, 3) for x in region_dts],
-                        "min_ms_per_step": round(min(region_dts) / args.steps * 1e3, 3),
-                        "median_ms_per_step": round(ms_per_step, 3),
-                        "max_ms_per_step": round(max(region_dts) / args.steps * 1e3, 3),
-                        "value_min": round(views_per_step * K * args.steps / max(region_dts), 2),
-                        "value_max": round(views_per_step * K * args.steps / min(region_dts), 2),
-                        "note": "the timed region (exactly `steps` steps between barriers) run three times back to back; "
-                                "value / ms_per_step are the median region's"},
+                       "allreduce_ms_per_step": None if allreduce_ms is None else round(allreduce_ms, 3)},
             "build_id": _lib.build_id(),
-            "stages": stages,
         }
+        stages = None
+        if args.full:
+            # R from a state-level forward (the operator keeps it in its autograd ctx)
+            with torch.no_grad():
+                wv, fp, cc = motion.get_trajectory_matrices(0)
+                rs = dgr.GaussianRasterizationSettings(H, W, scene["tanfovx"], scene["tanfovy"],
+                                                       torch.from_numpy(scene["bg"]).to(dev), 1.0, 0.2, 100.0, False,
+                                                       args.sh_degree, cc, False, False)
+                R_tot = dgr._forward_impl(K, cloud.get_xyz.detach(), cloud.get_features.detach().contiguous(), None,
+                                          cloud.get_opacity.detach().reshape(-1), cloud.get_scaling.detach(),
+                                          cloud.get_rotation.detach(), None, wv.contiguous(), fp.contiguous(),
+                                          cc.contiguous(), rs)[0]
+            bytes_by_stage = stage_bytes(P, Pv_tot, R_tot * frac_k, N, K * frac_k, s)
+            stages = {}
+            for name, (ms, calls) in prof.items():
+                if calls == 0:
+                    continue
+                avg_ms = ms / calls
+                gbs = bytes_by_stage[name] / (avg_ms * 1e-3) / 1e9
+                # model_GBps: the byte MODEL of SURVEY 8d over the measured time -- not achieved bandwidth (for geometry_bwd the
+                # model counts the K-summed Pv reads the fused kernel does not repeat); traffic_* (below) is counter-based
+                stages[name] = {"avg_ms": round(avg_ms, 4), "launches": calls, "alg_bytes": int(bytes_by_stage[name]),
+                                "model_GBps": round(gbs, 1), "ms_per_step": round(ms / max(stats["profiled_steps"], 1), 4),
+                                "traffic_bytes": None, "traffic_GBps": None}
+                if name == "contrib_reduce":
+                    moved = 48 * R_tot * frac_k + 64 * Pv_tot
+                    stages[name]["moved_bytes"] = int(moved)
+                    stages[name]["moved_GBps"] = round(moved / (avg_ms * 1e-3) / 1e9, 1)
+            # counter-based HBM bytes per step and stage: the committed FETCH_SIZE / WRITE_SIZE passes of this same command
+            # (profiles/traffic_rNN.json, `_per_step`; PMC counters cannot be collected from inside this process), over THIS
+            # run's stage times -- same provenance rule as roofline.traffic
+            traffic_doc, traffic_file = None, None
+            import glob as _glob
+            for path in sorted(_glob.glob(os.path.join(ROOT, "profiles", "traffic_r[0-9][0-9].json")))[::-1]:
+                try:
+                    doc = json.load(open(path))
+                except Exception:
+                    continue
+                if doc.get("_config") == args.config and "_per_step" in doc and world == 1 and emu is None \
+                        and args.sh_degree == doc.get("_sh_degree", 2):
+                    traffic_doc, traffic_file = doc, os.path.basename(path)
+                    break
+            if traffic_doc is not None:
+                for name, nbytes in traffic_doc["_per_step"].items():
+                    if name in stages and stages[name]["ms_per_step"] > 0:
+                        stages[name]["traffic_bytes"] = int(nbytes)
+                        stages[name]["traffic_GBps"] = round(nbytes / (stages[name]["ms_per_step"] * 1e-3) / 1e9, 1)
+            dom = max(stages, key=lambda n: stages[n]["avg_ms"])
+            total_bytes = sum(bytes_by_stage.values())
+            result["config"].update({
+                # csrc/api.hip: how many parts the timed region's compositing backward ran in (1 = one launch; > 1: a
+                # large view enqueued eagerly, each part's row totals on a side stream beside the next part's
+                # compositing, bit-identical -- DESIGN.md 7); the per-stage averages below are taken with the stage
+                # timers on, i.e. with ONE launch per step
+                # and only for eagerly enqueued steps: the library does not fork inside a stream capture (a forked
+                # executable graph does not give its memory back on this runtime, tools/graph_fork_leak.hip)
+                "backward_in_parts": (int(_lib.lib().dgs_backward_parts(_lib.context(), int(round(K * frac_k)), int(R_tot * frac_k),
+                                                                        int(bool(dgr.TILE_CULL)))) if
+                                      (not graph_info or _lib.context_overlap_mode() == 3) else 1),
+                "profiled_region_ms_per_step": stats.get("profiled_ms_per_step"),
+                "Pv_total": Pv_tot, "R_total": int(R_tot),
+                "pixel_gaussian_evals_upper_bound_per_step": int(256 * R_tot)})
+            result.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": stages[dom]["model_GBps"], "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(stages[dom]["model_GBps"] / HBM_PEAK_GBS, 5), "traffic": None,
+                             "alg_bytes_per_launch": stages[dom]["alg_bytes"], "avg_launch_ms": stages[dom]["avg_ms"],
+                             "avg_launch_ms_source": "HIP events on the launch stream inside this run (dgs_profile_*)" +
+                                                     (", recorded in the eager region that follows the replayed one" if graph_info else "") +
+                                                     "; with the stage timers on the compositing backward runs as ONE launch "
+                                                     "per step (as it does inside a captured graph; an eagerly enqueued step "
+                                                     "runs it in parts, see config.backward_in_parts), and "
+                                                     "profiles/r06_kernel_stats.csv is taken the same way (DGS_BWD_OVERLAP=0)",
+                             "note": "the dominant kernel (compositing) is bound by VALU issue, not by HBM (SURVEY 8d): `frac` is "
+                                     "the honest HBM fraction of its byte model, `valu` (when the round's PMC profile of this "
+                                     "config is committed) the fraction of the VALU issue peak it reaches"},
+                "pipeline_hbm": {"alg_bytes_per_step": int(total_bytes),
+                                 "model_GBps": round(total_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+                                 "frac": round(total_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                 # counter-based: every kernel of the step (loss image and Adam included), committed passes
+                                 "traffic_bytes_per_step": (int(traffic_doc["_per_step_total"]) if traffic_doc is not None
+                                                            else None),
+                                 "traffic_GBps": (round(traffic_doc["_per_step_total"] / (ms_per_step * 1e-3) / 1e9, 1)
+                                                  if traffic_doc is not None else None),
+                                 "traffic_source": (f"profiles/{traffic_file}: {traffic_doc.get('_source', '')}"
+                                                    if traffic_doc is not None else None)},
+                "regions": {"ms_per_step": [round(x / args.steps * 1e3, 3) for x in region_dts],
+                            "min_ms_per_step": round(min(region_dts) / args.steps * 1e3, 3),
+                            "median_ms_per_step": round(ms_per_step, 3),
+                            "max_ms_per_step": round(max(region_dts) / args.steps * 1e3, 3),
+                            "value_min": round(views_per_step * K * args.steps / max(region_dts), 2),
+                            "value_max": round(views_per_step * K * args.steps / min(region_dts), 2),
+                            "note": "the timed region (exactly `steps` steps between barriers) run three times back to back; "
+                                    "value / ms_per_step are the median region's"},
+                "stages": stages,
+            })
         if fwd_only is not None:
             result["forward_only_renders_per_s"] = fwd_only["value"]
             result["forward_only"] = fwd_only
@@ -892,7 +970,7 @@ def run_rank(args):
         import glob
         for stem, key in (("traffic", "traffic"), ("valu", "valu")):
             found = sorted(glob.glob(os.path.join(ROOT, "profiles", f"{stem}_r[0-9][0-9].json")))    # the newest round's
-            if not found or world != 1 or emu is not None:
+            if not args.full or not found or world != 1 or emu is not None:
                 continue
             path = found[-1]
             fname = os.path.basename(path)
@@ -919,7 +997,7 @@ def run_rank(args):
                             "source": f"profiles/{fname}: {doc.get('_source', '')}"}
             except Exception:
                 pass
-        if world == 1 and emu is None and not args.no_cpu_baseline:
+        if args.full and world == 1 and emu is None and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_port(scene, K // 2)
             try:
                 result["cpu_baseline_torch_naive"] = cpu_baseline_torch_naive(scene, K // 2)
@@ -928,7 +1006,7 @@ def run_rank(args):
     else:
         result = None
     hung = False
-    if world > 1 and not args.no_extras and not args.autograd_path:
+    if args.full and world > 1 and not args.no_extras and not args.autograd_path:
         import threading
         extras = {}
 

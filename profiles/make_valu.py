@@ -2,7 +2,7 @@
 
     rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE \
         SQ_LDS_BANK_CONFLICT -d <dir> --output-format csv \
-        -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-reference-lists --no-graph
+        -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-reference-lists --no-graph
     rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAVES -d <dir2> ... -- tools/valu_rate 8
     python profiles/make_valu_peak.py <dir2> profiles/valu_classes_<round>.txt > profiles/valu_peak_<round>.json
     python tools/isa_census.py --json profiles/isa_census_<round>.json
@@ -51,7 +51,7 @@ if os.path.exists(cen_file):
 
 out = {"_config": sys.argv[2] if len(sys.argv) > 2 else "metric",
        "_source": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES GRBM_GUI_ACTIVE "
-                  "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline "
+                  "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline "
                   "--no-reference-lists --no-graph (metric config); class costs: "
                   f"profiles/valu_peak_{rnd}.json (tools/valu_rate under the same counters); mix: profiles/isa_census_{rnd}.json",
        "_unit": "per launch; GRBM_GUI_ACTIVE is summed over the 8 XCDs; ipc_per_simd = SQ_INSTS_VALU / (1024 SIMDs * "

@@ -1280,7 +1280,7 @@ def test_two_ranks_bench_in_the_drivers_launch_form(gpu):
         port = s.getsockname()[1]
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                 "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--config",
-                "cfg2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], env)
+                "cfg2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"], env)
     lines = [ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln]
     assert len(lines) == 1, out[-2000:]                       # rank 0 prints, the others stay silent
     line = json.loads(lines[0])
@@ -1322,6 +1322,48 @@ def test_emulated_shard_slice_of_the_bench(gpu):
     assert got["subframes"]["ms_per_step"] < got["views"]["ms_per_step"]
 
 
+def test_bench_plain_run_dump_and_full(gpu, tmp_path):
+    """A plain bench run times --steps steps once and prints the metric contract only; --dump-outputs writes what the last
+    timed step computed (float32 / float64, under 64 MB), the same bits on a second run with the same arguments; --full adds
+    the three regions, the stage timings and the side regions."""
+    import json
+    import os
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DGS_DIST_BACKEND", "DGS_DIST_ONE_DEVICE"):
+        env.pop(k, None)
+    common = [sys.executable, os.path.join(root, "bench.py"), "--config", "cfg2", "--steps", "4", "--warmup", "2"]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = _run(common + ["--dump-outputs", str(d)], env)
+        line = json.loads([ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+            assert key in line, key
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f32"
+        for key in ("regions", "stages", "roofline", "cpu_baseline", "value_with_depth", "forward_only"):
+            assert key not in line, key
+        files = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert all(f.endswith(".npy") for f in files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        for name in ("param_xyz", "exp_avg_xyz", "exp_avg_sq_f_rest", "stats_xyz_gradient_accum", "loss_l1"):
+            assert name + ".npy" in files, name
+        assert np.abs(files["exp_avg_xyz.npy"]).max() > 0         # the moments carry the steps' gradients
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    out = _run(common + ["--full", "--no-cpu-baseline"], env)
+    line = json.loads([ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
+    assert len(line["regions"]["ms_per_step"]) == 3 and abs(line["regions"]["median_ms_per_step"] - line["ms_per_step"]) < 1e-6
+    assert "composite_bwd" in line["stages"] and line["roofline"]["kernel"] in line["stages"]
+    assert line["value_with_depth"]["depth_output"] is True and line["forward_only"]["value"] > 0
+    assert line["config"]["R_total"] > 0 and "cpu_baseline" not in line
+
+
 def test_bench_line_survives_an_extra_region_that_never_returns(gpu):
     """The regions behind the headline one (other sharding mode, all-reduce A/B) run under a watchdog AFTER rank 0 has
     assembled the headline's result: with the watchdog's patience set to (almost) nothing the line must still come out,
@@ -1332,7 +1374,7 @@ def test_bench_line_survives_an_extra_region_that_never_returns(gpu):
     import sys
     root, tool, env = _two_rank_env(DGS_BENCH_EXTRAS_TIMEOUT_S="0.01")
     out = _run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "cfg2", "--steps", "3",
-                "--warmup", "1", "--no-cpu-baseline"], env, rc=3)
+                "--warmup", "1", "--no-cpu-baseline", "--full"], env, rc=3)
     line = json.loads([ln for ln in out.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["config"]["per_rank"] is not None
     assert "did not return" in line["extras"].get("error", ""), line["extras"]

@@ -398,7 +398,7 @@ def test_poll_charges_every_overflow_to_its_own_step():
 
 
 def test_rccl_log_parser_reads_version_algorithm_and_topology(tmp_path):
-    """bench.py --gpus N writes every rank's RCCL log to a file (NCCL_DEBUG=INFO, set before init) and reports what the
+    """bench.py --gpus N --full writes every rank's RCCL log to a file (NCCL_DEBUG=INFO, set before init) and reports what the
     library chose ("verify which algorithm it picks").  The parser on a log in NCCL's / RCCL's INFO format."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("dgs_bench", os.path.join(ROOT, "bench.py"))
@@ -443,3 +443,16 @@ def test_rccl_log_parser_reads_version_algorithm_and_topology(tmp_path):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def test_bench_options_plain_full_and_dump():
+    """A plain bench run is the headline only; --full and --dump-outputs DIR are opt-in."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("dgs_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out_dir"])
+    assert a.full is True and a.dump_outputs == "out_dir"
+    assert bench.DUMP_MAX_BYTES == 64 << 20

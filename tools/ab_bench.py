@@ -29,7 +29,7 @@ def main():
             env = dict(os.environ)
             if lib != "default":
                 env["DGS_LIB_PATH"] = os.path.abspath(lib)
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "5",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", steps, "--warmup", "5",
                                 "--config", config, "--no-cpu-baseline", "--no-reference-lists"] + extra, env=env,
                                capture_output=True, text=True)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -16,6 +16,6 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE
            "SQ_IFETCH SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE" \
            "SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VMEM SQ_WAVES SQ_INSTS_VALU_TRANS SQ_INSTS_VALU_MFMA_F32"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set -d $out/p$i -o pmc --output-format csv -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-reference-lists --no-graph > $out/p$i.log 2>&1 || echo "pass $i failed"
+  rocprofv3 --kernel-trace --pmc $set -d $out/p$i -o pmc --output-format csv -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-reference-lists --no-graph > $out/p$i.log 2>&1 || echo "pass $i failed"
 done
 python3 profiles/pmc_summary.py $out | grep -i "composite"

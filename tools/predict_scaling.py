@@ -56,7 +56,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "predicted_scaling.json"))
     a = ap.parse_args()
     from deblurgs_amd.sharding import shard_range
-    common = ["--config", a.config, "--steps", str(a.steps), "--warmup", str(a.warmup)]
+    common = ["--full", "--config", a.config, "--steps", str(a.steps), "--warmup", str(a.warmup)]
     base = run_bench(common + ["--no-cpu-baseline", "--no-reference-lists"])
     K = int(base["config"]["workload"].split("K=")[1].split(" ")[0])
     t1 = base["ms_per_step"]

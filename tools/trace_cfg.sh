@@ -7,7 +7,7 @@ cd $root
 export TMPDIR=/tmp
 out=$root/gpurun_out/trace_$cfg
 mkdir -p $out
-rocprofv3 --kernel-trace --stats -d $out/trace -o trace --output-format csv -- python3 bench.py --config $cfg --steps 50 --warmup 5 --no-cpu-baseline --no-reference-lists "$@" > $out/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/trace -o trace --output-format csv -- python3 bench.py --full --config $cfg --steps 50 --warmup 5 --no-cpu-baseline --no-reference-lists "$@" > $out/trace.log 2>&1
 python3 - "$out" <<'PY'
 import csv, sys, glob
 out = sys.argv[1]
