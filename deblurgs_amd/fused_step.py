@@ -37,10 +37,8 @@ import torch
 
 from . import _lib
 from . import diff_gaussian_rasterization as dgr
-
-
-def _ptr(t, offset_elems=0):
-    return None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * offset_elems)
+from . import raster_call
+from .raster_call import _ptr, _stream
 
 
 class CaptureRefused(RuntimeError):
@@ -110,9 +108,7 @@ class FusedStep:
                 # -- the pinned block baked into a graph is rewritten by every later replay of the same view while the host
                 # runs several replays ahead, so it can never say which replay overflowed (with two views in
                 # flight a running drop counter read from those blocks went backwards and queued 2^32 - 1 retries).
-                R, hi, overflow = (int(x) & 0xFFFFFFFF for x in pnd.host[:3].tolist())
-                if hi != 0:
-                    raise RuntimeError("num_rendered exceeds 32 bits: render fewer subframes per call")
+                R, overflow, _ = raster_call.counts(pnd.host)
                 if pnd.speculative and overflow:
                     self.dropped += 1
                     self.retry.append(pnd.request)
@@ -141,15 +137,15 @@ class FusedStep:
         graph launch costs a hand-over between the copy engine and the compute queue, tens of microseconds per step."""
         slot = self._host_words()
         hbuf.numpy().view("uint64")[2] = slot.data_ptr()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().dgs_copy_words(ctypes.c_void_p(ent["hyper"].data_ptr()), ctypes.c_void_p(hbuf.data_ptr()),
-                                             int(hbuf.numel()), stream), "dgs_copy_words")
+        _lib.check(_lib.lib().dgs_copy_words(_ptr(ent["hyper"]), _ptr(hbuf), int(hbuf.numel()), _stream(dev)),
+                   "dgs_copy_words")
         return slot
 
     def _eager_is_faster(self, K, cap, cull):
-        if self.capture_large or _lib.context_overlap_mode() == 3:   # (3: the library forks inside a capture too)
+        dev = self.cloud._xyz.device.index     # (the context the step's backward runs with)
+        if self.capture_large or _lib.context_overlap_mode(dev) == 3:   # (3: the library forks inside a capture too)
             return False
-        if _lib.lib().dgs_backward_parts(_lib.context(), int(K), int(cap), int(bool(cull))) <= 1:
+        if _lib.lib().dgs_backward_parts(_lib.context(dev), int(K), int(cap), int(bool(cull))) <= 1:
             return False
         self.eager_preferred += 1
         return True
@@ -208,21 +204,16 @@ class FusedStep:
                 p.grad = torch.zeros_like(p)
         else:      # take part in the other ranks' (chunked) reduction of the gradient bucket with a bucket of zeros
             hot = list(cloud.hot_parameters())
-            sizes = [p.numel() for p in hot]
-            offs = [0]
-            for n in sizes:
-                offs.append(offs[-1] + (n + 3) // 4 * 4)
-            flat = torch.zeros(offs[-1], **f32)
-            for i, p in enumerate(hot):
-                p.grad = flat[offs[i]:offs[i] + sizes[i]].view(p.shape)
+            bucket = raster_call.Bucket([p.numel() for p in hot])
+            flat = torch.zeros(bucket.size, **f32)
+            for p, g in zip(hot, bucket.views(flat, [p.shape for p in hot])):
+                p.grad = g
             if int(ar.get("chunks", 1)) <= 1 or P < 512:
                 if P > 0:
                     sharding._allreduce(flat, ar.get("average", False), ar.get("group"))
             else:
-                widths = [n // max(P, 1) for n in sizes]
                 for b0, b1 in sharding.chunk_bounds(P, int(ar["chunks"])):
-                    sharding.allreduce_slices([flat[offs[i] + b0 * c:offs[i] + b1 * c] for i, c in enumerate(widths)],
-                                              ar.get("average", False), ar.get("group"))
+                    sharding.allreduce_slices(bucket.chunk(flat, P, b0, b1), ar.get("average", False), ar.get("group"))
         if m.is_optimizing():
             m._trans._control_points.grad, m._rot._control_points.grad = torch.zeros_like(ct_all), torch.zeros_like(cr_all)
             if nu_raw.numel() > 0:
@@ -265,54 +256,24 @@ class FusedStep:
 
         Returns the result dict of run(), or None when this step cannot be replayed yet (no duplicate count learnt for
         the view: the caller runs the eager step, which learns it)."""
+        plan = self._replay_plan(cam_idx, subframe_indice)
+        if plan is None:
+            return None
+        K_total, ckey, cap, cull = plan
         cloud, m = self.cloud, self.motion
-        dev = cloud._xyz.device
-        f = m.n_subframes
-        self._poll()
-        K_total = f if (isinstance(subframe_indice, str) and subframe_indice == "all") else (
-            int(subframe_indice) if isinstance(subframe_indice, int) else len(subframe_indice))
-        ckey = (int(cam_idx), K_total, 0)
-        cap = self._capacity(ckey) if self.speculative else None
-        if cap is None or isinstance(subframe_indice, (list, tuple)) or torch.is_tensor(subframe_indice):
-            return None
-        q = 1 << max(cap.bit_length() - 5, 10)      # quantised to ~3-6 %: small count drifts do not force a re-capture
-        cap = -(-cap // q) * q
-        hot = list(cloud.hot_parameters())
-        cull = dgr.TILE_CULL if self.tile_cull is None else bool(self.tile_cull)
-        if self._eager_is_faster(K_total, cap, cull):
-            return None
         gkey = (int(cam_idx), subframe_indice, int(cloud.active_sh_degree), bool(m.is_optimizing()),
                 bool(m.curve_random_sample), cap, self._generation, gt.data_ptr(), bool(cull), bool(dgr.WIDE_RECORDS),
-                tuple(p.data_ptr() for p in hot), tuple(signature),
+                tuple(p.data_ptr() for p in cloud.hot_parameters()), tuple(signature),
                 tuple(t.data_ptr() for t in stats) if stats is not None else (), bool(self.always_depth))
         ent = self._graphs.get(gkey)
         if ent is None:
             ent = self._capture(gkey, cam_idx, gt, subframe_indice, cap, optimizer, tail, stats)
-        # ---- this step's scalars: host block -> device block (the ring keeps a block alive until its copy has run)
-        slot = self._ring[self._ring_pos % len(self._ring)] if self._ring else None
-        if slot is None or slot[0].numel() != ent["hyper"].numel():
-            self._ring = [(torch.zeros(ent["hyper"].numel(), dtype=torch.float32).pin_memory(), torch.cuda.Event())
-                          for _ in range(8)]
-            self._ring_pos = 0
-            slot = self._ring[0]
-        self._ring_pos += 1
-        hbuf, hev = slot
-        hev.synchronize()                      # (recorded 8 replays ago: never waits in practice)
-        hv = hbuf.numpy()
-        hv[0] = float(lambda_t)
-        hv[1:4] = (torch.rand(3) if background is None else background.detach().float().cpu()).numpy()   # motion.py:112-113
-        if m.curve_random_sample and f > 2:                               # scene/motion.py:213-214
-            hv[48:48 + f - 2] = (torch.rand(f - 2) if uniform is None else uniform.detach().float().cpu()).numpy()
+        hbuf, hev = self._scalar_slot(ent, lambda_t, background, uniform)
         for p, g in ent["grads"]:              # the step's gradients live in the graph's buffers
             p.grad = g
         optimizer.skip_flag_ptr = ent["result"]["skip_flag_ptr"]
-        optimizer.step_scalars(hv[8:8 + 2 * _lib.ADAM_MAX_GROUPS])
-        slot = self._push_scalars(ent, hbuf, dev)
-        hev.record(torch.cuda.current_stream(dev))
-        ent["graph"].replay()
-        self._track_replay(slot, ckey, (cam_idx, subframe_indice), cap, dev)
-        self.last_capacity = cap
-        self.replayed += 1
+        optimizer.step_scalars(hbuf.numpy()[8:8 + 2 * _lib.ADAM_MAX_GROUPS])
+        self._launch(ent, hbuf, hev, ckey, (cam_idx, subframe_indice), cap)
         return ent["result"]
 
     def replay_front(self, cam_idx, lambda_t, gt, subframe_indice, ar, background=None, uniform=None, shard=None,
@@ -332,9 +293,29 @@ class FusedStep:
 
         Returns run()'s result dict ('subframes', 'blur' and 'depths' are None in "views" mode: the images live in the
         graph's pool), or None when the step cannot be replayed yet (no duplicate count learnt for the view)."""
+        plan = self._replay_plan(cam_idx, subframe_indice, shard)
+        if plan is None:
+            return None
+        K_total, ckey, cap, cull = plan
         cloud, m = self.cloud, self.motion
-        dev = cloud._xyz.device
-        f = m.n_subframes
+        chunks = 1 if ar is None else int(ar.get("chunks", 1))
+        gkey = ("front", int(cam_idx), subframe_indice, int(cloud.active_sh_degree), bool(m.is_optimizing()),
+                bool(m.curve_random_sample), cap, self._generation, gt.data_ptr(), bool(cull), bool(dgr.WIDE_RECORDS),
+                tuple(p.data_ptr() for p in cloud.hot_parameters()), chunks, float(self.lambda_hinge),
+                None if shard is None else (int(shard[0]), int(shard[1])), bool(self.always_depth))
+        ent = self._graphs.get(gkey)
+        if ent is None:
+            ent = self._capture_front(gkey, cam_idx, gt, subframe_indice, cap, ar, K_total, shard)
+        hbuf, hev = self._scalar_slot(ent, lambda_t, background, uniform)
+        self._launch(ent, hbuf, hev, ckey, (cam_idx, subframe_indice), cap, background_dev, uniform_dev)
+        return ent["finish"](float(lambda_t))
+
+    def _replay_plan(self, cam_idx, subframe_indice, shard=None):
+        """What replay() and replay_front() settle before they look up a graph: (K_total, the capacity key, the capacity
+        quantised to ~3-6 % -- small count drifts do not force a re-capture --, tile culling); None when the step is not
+        replayed (no duplicate count learnt for the view, an explicit subframe list, an empty "subframes" slice, or a view
+        whose backward is faster enqueued eagerly)."""
+        f = self.motion.n_subframes
         self._poll()
         K_total = f if (isinstance(subframe_indice, str) and subframe_indice == "all") else (
             int(subframe_indice) if isinstance(subframe_indice, int) else len(subframe_indice))
@@ -350,18 +331,17 @@ class FusedStep:
             return None
         q = 1 << max(cap.bit_length() - 5, 10)
         cap = -(-cap // q) * q
-        hot = list(cloud.hot_parameters())
         cull = dgr.TILE_CULL if self.tile_cull is None else bool(self.tile_cull)
-        if shard is None and self._eager_is_faster(K_total, cap, cull):   # ("subframes": the captured front ends before the backward)
+        # ("subframes" sharding: the captured front ends before the backward)
+        if shard is None and self._eager_is_faster(K_total, cap, cull):
             return None
-        chunks = 1 if ar is None else int(ar.get("chunks", 1))
-        gkey = ("front", int(cam_idx), subframe_indice, int(cloud.active_sh_degree), bool(m.is_optimizing()),
-                bool(m.curve_random_sample), cap, self._generation, gt.data_ptr(), bool(cull), bool(dgr.WIDE_RECORDS),
-                tuple(p.data_ptr() for p in hot), chunks, float(self.lambda_hinge),
-                None if shard is None else (int(shard[0]), int(shard[1])), bool(self.always_depth))
-        ent = self._graphs.get(gkey)
-        if ent is None:
-            ent = self._capture_front(gkey, cam_idx, gt, subframe_indice, cap, ar, K_total, shard)
+        return K_total, ckey, cap, cull
+
+    def _scalar_slot(self, ent, lambda_t, background, uniform):
+        """This step's scalar block, filled in the next pinned slot of the ring (which keeps a block alive until its copy
+        has run): lambda_t, the background and the alignment jitter.  Returns (block, its event)."""
+        m = self.motion
+        f = m.n_subframes
         slot = self._ring[self._ring_pos % len(self._ring)] if self._ring else None
         if slot is None or slot[0].numel() != ent["hyper"].numel():
             self._ring = [(torch.zeros(ent["hyper"].numel(), dtype=torch.float32).pin_memory(), torch.cuda.Event())
@@ -370,82 +350,33 @@ class FusedStep:
             slot = self._ring[0]
         self._ring_pos += 1
         hbuf, hev = slot
-        hev.synchronize()
+        hev.synchronize()                      # (recorded 8 replays ago: never waits in practice)
         hv = hbuf.numpy()
         hv[0] = float(lambda_t)
-        hv[1:4] = (torch.rand(3) if background is None else background.detach().float().cpu()).numpy()
-        if m.curve_random_sample and f > 2:
+        hv[1:4] = (torch.rand(3) if background is None else background.detach().float().cpu()).numpy()   # motion.py:112-113
+        if m.curve_random_sample and f > 2:                               # scene/motion.py:213-214
             hv[48:48 + f - 2] = (torch.rand(f - 2) if uniform is None else uniform.detach().float().cpu()).numpy()
+        return hbuf, hev
+
+    def _launch(self, ent, hbuf, hev, ckey, request, cap, background_dev=None, uniform_dev=None):
+        """The scalar block to the graph, the replay, and the step on the pending list."""
+        dev = self.cloud._xyz.device
+        f = self.motion.n_subframes
         slot = self._push_scalars(ent, hbuf, dev)
         hev.record(torch.cuda.current_stream(dev))
         if background_dev is not None:               # (shared draws of a "subframes" step: device to device, stream-ordered)
             ent["hyper"][1:4].copy_(background_dev.reshape(3))
-        if uniform_dev is not None and m.curve_random_sample and f > 2:
+        if uniform_dev is not None and self.motion.curve_random_sample and f > 2:
             ent["hyper"][48:48 + f - 2].copy_(uniform_dev.reshape(f - 2))
         ent["graph"].replay()
-        self._track_replay(slot, ckey, (cam_idx, subframe_indice), cap, dev)
+        self._track_replay(slot, ckey, request, cap, dev)
         self.last_capacity = cap
         self.replayed += 1
-        return ent["finish"](float(lambda_t))
 
-    def _capture_front(self, gkey, cam_idx, gt, subframe_indice, cap, ar, K_total, shard=None):
-        cloud, m = self.cloud, self.motion
-        dev = cloud._xyz.device
-        f = m.n_subframes
-        if len(self._graphs) >= self.max_graphs:
-            self._graphs.pop(next(iter(self._graphs)))
-        hyper = torch.zeros(self._hyper_words(f), dtype=torch.float32, device=dev)
-        host = torch.zeros(8, dtype=torch.int32).pin_memory()
-        self._drop_counter(dev)
-        if self._release_pool:
-            self._release_pool = False
-            self._keep = None
-            torch.cuda.synchronize(dev)
-            torch.cuda.empty_cache()
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        ent = {"hyper": hyper, "host": host, "status": torch.zeros(4, dtype=torch.int32, device=dev)}
-        # What the eager part and the caller read after a replay lives OUTSIDE the capture pool, shared by all graphs of a
-        # cloud generation (steps never overlap): the gradient bucket, the loss values, the skip word, and -- sharded runs
-        # update the densification statistics in a launch of their own -- the radii and the screen-space gradients.
-        Mr_, P_ = cloud._features_rest.shape[1], cloud._xyz.shape[0]
-        n_bucket = sum((n + 3) // 4 * 4 for n in (3 * P_, 3 * P_, 3 * Mr_ * P_, P_, 3 * P_, 4 * P_))
-        if self._bucket is None or self._bucket[0] != self._generation or self._bucket[1] != n_bucket:
-            self._bucket = (self._generation, n_bucket, torch.empty(n_bucket, dtype=torch.float32, device=dev))
-        skey = (self._generation, K_total, P_)
-        if self._front_shared is None or self._front_shared[0] != skey:
-            self._front_shared = (skey, torch.empty((K_total, P_), dtype=torch.int32, device=dev),
-                                  torch.empty((K_total, P_, 3), dtype=torch.float32, device=dev),
-                                  torch.zeros(1, dtype=torch.int32, device=dev))
-        ent["work"] = torch.zeros(8, dtype=torch.float32, device=dev)
-        cap_args = {"capacity": cap, "host": host, "status": ent["status"], "lambda_ptr": hyper.data_ptr(),
-                    "work": ent["work"], "bucket": self._bucket[2], "split": "composite" if shard is None else "forward",
-                    "radii": self._front_shared[1],
-                    "means2D": self._front_shared[2], "skipw": self._front_shared[3], "tail": None}
-        bg = hyper[1:4]
-        uniform = hyper[48:48 + f - 2] if (m.curve_random_sample and f > 2) else None
-        for p in list(cloud.hot_parameters()) + (list(m.parameters()) if m.is_optimizing() else []):
-            p.grad = None
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
-                front = self.run(cam_idx, 0.0, gt, bg, subframe_indice, uniform=uniform, _cap=cap_args, ar=ar, shard=shard)
-        except RuntimeError as ex:
-            raise CaptureRefused(str(ex)) from ex
-        # the step's large buffers go back to the pool (the other views' captures re-use the blocks); finish() reaches them
-        # through the raw pointers of its DgsProblem / DgsBackwardIO -- valid until the next replay of ANY graph of the pool,
-        # which is enqueued after this step's eager part on the same stream
-        front["big"][0] = None
-        if "fwd_big" in front:
-            front["fwd_big"][0] = None
-        ent["graph"], ent["finish"], ent["keep"] = graph, front["finish"], front["_keep"]
-        self._keep = None
-        self._graphs[gkey] = ent
-        self.captured += 1
-        return ent
-
-    def _capture(self, gkey, cam_idx, gt, subframe_indice, cap, optimizer, tail, stats=None):
+    def _capture_setup(self, cap, optimizer=None):
+        """What both captures allocate OUTSIDE the capture pool before they record: the scalar block, the pinned count
+        words, the status words, the drop counter, the loss kernel's work block and the gradient bucket.  Returns (ent,
+        the run() arguments of a capture, the background and the alignment jitter as views of the scalar block)."""
         cloud, m = self.cloud, self.motion
         dev = cloud._xyz.device
         f = m.n_subframes
@@ -462,44 +393,80 @@ class FusedStep:
         if self._pool is None:
             self._pool = torch.cuda.graph_pool_handle()
         ent = {"hyper": hyper, "host": host, "status": torch.zeros(4, dtype=torch.int32, device=dev)}
-        # Two things a replay leaves behind live OUTSIDE the capture pool (ordinary allocations made before the capture):
-        # the loss kernel's work block -- `losses` handed to the caller is a view of it and holds a replay's two values until
-        # the SAME graph is replayed again (in the pool it could be another graph's scratch: all graphs share the pool) --
-        # and the gradient bucket, ONE per cloud generation for all graphs (replays never overlap and the optimiser launch
-        # at the end of a replay has consumed the gradients; a bucket per graph would be 236 MB per view at P = 1M, SH 3).
-        Mr_ = cloud._features_rest.shape[1]
-        P_ = cloud._xyz.shape[0]
-        n_bucket = sum((n + 3) // 4 * 4 for n in (3 * P_, 3 * P_, 3 * Mr_ * P_, P_, 3 * P_, 4 * P_))
+        # The gradient bucket is ONE per cloud generation for all graphs (replays never overlap and what reads the
+        # gradients -- the optimiser launch at the end of a replay, a front's eager part -- has consumed them before the next
+        # replay; a bucket per graph would be 236 MB per view at P = 1M, SH 3).  The loss kernel's work block is one per
+        # graph: `losses` handed to the caller is a view of it and holds a replay's two values until the SAME graph is
+        # replayed again (in the pool it could be another graph's scratch: all graphs share the pool).
+        n_bucket = raster_call.cloud_bucket(cloud._xyz.shape[0], cloud._features_rest.shape[1]).size
         if self._bucket is None or self._bucket[0] != self._generation or self._bucket[1] != n_bucket:
             self._bucket = (self._generation, n_bucket, torch.empty(n_bucket, dtype=torch.float32, device=dev))
         ent["work"] = torch.zeros(8, dtype=torch.float32, device=dev)
         cap_args = {"capacity": cap, "host": host, "status": ent["status"], "lambda_ptr": hyper.data_ptr(),
-                    "work": ent["work"], "bucket": self._bucket[2],
-                    "tail": (lambda fr: tail(fr, hyper.data_ptr() + 4 * 8)) if tail is not None else None}
-        bg = hyper[1:4]
-        uniform = hyper[48:48 + f - 2] if (m.curve_random_sample and f > 2) else None
+                    "work": ent["work"], "bucket": self._bucket[2]}
         params = list(cloud.hot_parameters()) + (list(m.parameters()) if m.is_optimizing() else [])
-        optimizer.ensure_state(params)
+        if optimizer is not None:
+            optimizer.ensure_state(params)
         for p in params:
             p.grad = None
+        uniform = hyper[48:48 + f - 2] if (m.curve_random_sample and f > 2) else None
+        return ent, cap_args, hyper[1:4], uniform, params
+
+    def _register(self, gkey, ent, graph):
+        ent["graph"] = graph
+        self._keep = None
+        self._graphs[gkey] = ent
+        self.captured += 1
+        return ent
+
+    def _capture_front(self, gkey, cam_idx, gt, subframe_indice, cap, ar, K_total, shard=None):
+        dev = self.cloud._xyz.device
+        ent, cap_args, bg, uniform, _ = self._capture_setup(cap)
+        # sharded runs update the densification statistics in a launch of their own: the radii, the screen-space gradients
+        # and the skip word live outside the pool too, shared by all graphs of a cloud generation
+        P = self.cloud._xyz.shape[0]
+        skey = (self._generation, K_total, P)
+        if self._front_shared is None or self._front_shared[0] != skey:
+            self._front_shared = (skey, torch.empty((K_total, P), dtype=torch.int32, device=dev),
+                                  torch.empty((K_total, P, 3), dtype=torch.float32, device=dev),
+                                  torch.zeros(1, dtype=torch.int32, device=dev))
+        cap_args.update(split="composite" if shard is None else "forward", radii=self._front_shared[1],
+                        means2D=self._front_shared[2], skipw=self._front_shared[3], tail=None)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
+                front = self.run(cam_idx, 0.0, gt, bg, subframe_indice, uniform=uniform, _cap=cap_args, ar=ar, shard=shard)
+        except RuntimeError as ex:
+            raise CaptureRefused(str(ex)) from ex
+        # the step's large buffers go back to the pool (the other views' captures re-use the blocks); finish() reaches them
+        # through the raw pointers of its DgsProblem / DgsBackwardIO -- valid until the next replay of ANY graph of the pool,
+        # which is enqueued after this step's eager part on the same stream
+        front["big"][0] = None
+        if "fwd_big" in front:
+            front["fwd_big"][0] = None
+        ent["finish"], ent["keep"] = front["finish"], front["_keep"]
+        return self._register(gkey, ent, graph)
+
+    def _capture(self, gkey, cam_idx, gt, subframe_indice, cap, optimizer, tail, stats=None):
+        dev = self.cloud._xyz.device
+        ent, cap_args, bg, uniform, params = self._capture_setup(cap, optimizer)
+        hyper = ent["hyper"]
+        cap_args["tail"] = (lambda fr: tail(fr, hyper.data_ptr() + 4 * 8)) if tail is not None else None
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
             fr = self.run(cam_idx, 0.0, gt, bg, subframe_indice, uniform=uniform, _cap=cap_args, stats=stats)
         # What a replay leaves behind for the host is the two loss values, the count words (pinned) and the gradients of
-        # the parameters (the first and the last allocated outside the pool, above); everything else the step allocated
+        # the parameters (the first and the last allocated outside the pool, by _capture_setup); everything else the step allocated
         # is released to the pool here, so that the captures of the other views re-use the same blocks (every replay is a
         # complete step: nothing of one replay is read after the next has started) -- the pool holds ONE step's buffers,
         # not one set per view.
-        ent["graph"] = graph
         ent["result"] = {"losses": fr["losses"], "K": fr["K"], "skip_flag_ptr": fr["skip_flag_ptr"], "blur": None,
                          "radii": None, "viewspace_grad": None, "subframes": None, "depths": None, "depth_tv": None}
         ent["grads"] = [(p, p.grad) for p in params if p.grad is not None]
         del fr
-        self._keep = None
-        self._graphs[gkey] = ent
-        self.captured += 1
-        return ent
+        return self._register(gkey, ent, graph)
 
     # ------------------------------------------------------------------------------------------------- the step
     @torch.no_grad()
@@ -532,7 +499,7 @@ class FusedStep:
         cloud, m = self.cloud, self.motion
         dev = cloud._xyz.device
         stream_obj = torch.cuda.current_stream(dev)
-        stream = ctypes.c_void_p(stream_obj.cuda_stream)
+        stream = _stream(dev)
         f32 = dict(dtype=torch.float32, device=dev)
         f = m.n_subframes
         cam = int(cam_idx)
@@ -604,21 +571,14 @@ class FusedStep:
         image = torch.empty(L.dgs_image_state_bytes(W, H, K), dtype=torch.uint8, device=dev)
         bg = background.to(dev, torch.float32).contiguous()
         cull = dgr.TILE_CULL if self.tile_cull is None else bool(self.tile_cull)
-        prob = _lib.DgsProblem()
-        prob.context = _lib.context(dev.index)
-        prob.P, prob.D, prob.M, prob.W, prob.H, prob.K = P, int(cloud.active_sh_degree), 1 + Mr, W, H, K
-        prob.tanfovx, prob.tanfovy = math.tan(m.ref_cam.FoVx * 0.5), math.tan(m.ref_cam.FoVy * 0.5)
-        prob.scale_modifier, prob.z_near, prob.z_far = 1.0, float(cloud.z_near), float(cloud.z_far)
-        prob.use_sigmoid, prob.prefiltered, prob.debug = int(bool(cloud.use_sigmoid)), 0, 0
-        prob.tile_cull, prob.scale_lb = int(cull), float(cloud.scale_lower_bound)
-        prob.raw_params = 3 if getattr(cloud, "use_isotrophic", False) else 1
-        prob.means3D, prob.shs, prob.shs_rest = _ptr(cloud._xyz), _ptr(cloud._features_dc), _ptr(rest)
-        prob.opacities, prob.scales, prob.rotations = _ptr(cloud._opacity), _ptr(cloud._scaling), _ptr(cloud._rotation)
-        prob.viewmatrix, prob.projmatrix, prob.campos, prob.bg = _ptr(view), _ptr(full), _ptr(campos), _ptr(bg)
-        prob.geom_state, prob.geom_bytes = ctypes.c_void_p(geom.data_ptr()), geom.numel()
-        prob.image_state, prob.image_bytes = ctypes.c_void_p(image.data_ptr()), image.numel()
-        out = _lib.DgsForwardOut()
-        out.out_color, out.out_depth, out.radii = _ptr(color), _ptr(depth), ctypes.c_void_p(radii.data_ptr())
+        rs = dgr.GaussianRasterizationSettings(
+            image_height=H, image_width=W, tanfovx=math.tan(m.ref_cam.FoVx * 0.5), tanfovy=math.tan(m.ref_cam.FoVy * 0.5),
+            bg=bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
+            sh_degree=cloud.active_sh_degree, campos=campos, prefiltered=False, debug=False)
+        raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
+        # (compact duplicate records always: wide_records = 0)
+        prob = raster_call.problem(K, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
+                                   None, view, full, campos, rs, bg, cull, 0, raw=raw, geom=geom, image=image)
         key = (cam, K_total, k0)
         if _cap is None:
             host = self._host_words()
@@ -627,28 +587,15 @@ class FusedStep:
             pnd = _Pending()
             pnd.host, pnd.speculative, pnd.key, pnd.generation = host, cap is not None, key, self._generation
             pnd.request = (cam_idx, subframe_indice)
+            out = raster_call.forward_out(color, depth, radii, host)
         else:
             host, cap, pnd = _cap["host"], int(_cap["capacity"]), None
-            out.drop_counter = ctypes.c_void_p(self._drop_counter(dev).data_ptr())
-            out.status_dev = ctypes.c_void_p(_cap["status"].data_ptr())
-            out.status_host_indirect = ctypes.c_void_p(_cap["lambda_ptr"] + 16)     # words [4:6] of the scalar block
-        out.num_rendered_host = ctypes.c_void_p(host.data_ptr())
-        if cap is not None:
-            binning = torch.empty(L.dgs_binning_state_bytes(cap, W, H, K), dtype=torch.uint8, device=dev)
-            prob.binning_state, prob.binning_bytes = ctypes.c_void_p(binning.data_ptr()), binning.numel()
-            _lib.check(L.dgs_forward(ctypes.byref(prob), ctypes.byref(out), cap, stream), "dgs_forward")
-            R = cap
-            skip_ptr = geom.data_ptr() + _lib.layout(P, W, H, K, 0).num_rendered + 20
-        else:   # exact two-phase forward: one blocking read of the count (also how the first capacity is learnt)
-            _lib.check(L.dgs_forward_geometry(ctypes.byref(prob), ctypes.byref(out), stream), "dgs_forward_geometry")
-            stream_obj.synchronize()
-            if int(host[1].item()) != 0:
-                raise RuntimeError("num_rendered exceeds 32 bits: render fewer subframes per call")
-            R = int(host[0].item()) & 0xFFFFFFFF
-            binning = torch.empty(L.dgs_binning_state_bytes(R, W, H, K), dtype=torch.uint8, device=dev)
-            prob.binning_state, prob.binning_bytes = ctypes.c_void_p(binning.data_ptr()), binning.numel()
-            _lib.check(L.dgs_forward_render(ctypes.byref(prob), ctypes.byref(out), R, stream), "dgs_forward_render")
-            skip_ptr = None
+            out = raster_call.forward_out(color, depth, radii, host, drop_counter=self._drop_counter(dev),
+                                          status_dev=_cap["status"],
+                                          status_host_indirect=_cap["lambda_ptr"] + 16)   # words [4:6] of the scalar block
+        # capacity None: the exact two-phase forward, one blocking read of the count (also how the first capacity is learnt)
+        R, binning = raster_call.forward(dev, prob, out, host, cap)
+        skip_ptr = None if cap is None else geom.data_ptr() + raster_call.skip_word_offset(P, W, H, K)
         if pnd is not None:
             pnd.capacity = R
             pnd.event = torch.cuda.Event()
@@ -667,6 +614,7 @@ class FusedStep:
                 _cap["skipw"].copy_(fwd_skip[0])
                 fwd_skip[0] = _cap["skipw"]
         del geom, image, binning
+        bucket = raster_call.cloud_bucket(P, Mr)      # the layout of this step's gradient bucket
 
         # Everything after the forward.  Eager steps run it right away.  A "subframes"-sharded step replayed by replay_front
         # captures only what precedes it (its first collective is the loss block) and calls it after every replay; a
@@ -697,24 +645,12 @@ class FusedStep:
                 blur = None
 
             # ---- backward: one flat gradient bucket in optimiser-group order (as _RasterizeCloudK.backward)
-            sizes = [3 * P, 3 * P, 3 * Mr * P, P, 3 * P, 4 * P]
-            offs = [0]
-            for n in sizes:
-                offs.append(offs[-1] + (n + 3) // 4 * 4)
-            flat = torch.empty(offs[-1], **f32) if _cap is None else _cap["bucket"]
-            assert flat.numel() == offs[-1]
-            seg = lambda i, shape: flat[offs[i]:offs[i] + sizes[i]].view(shape)
-            g_xyz, g_dc, g_op, g_sc, g_rot = (seg(0, (P, 3)), seg(1, cloud._features_dc.shape), seg(3, cloud._opacity.shape),
-                                              seg(4, (P, 3)), seg(5, (P, 4)))
-            g_rest = seg(2, cloud._features_rest.shape)
+            flat = torch.empty(bucket.size, **f32) if _cap is None else _cap["bucket"]
+            assert flat.numel() == bucket.size
+            g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = bucket.views(flat, [
+                (P, 3), cloud._features_dc.shape, cloud._features_rest.shape, cloud._opacity.shape, (P, 3), (P, 4)])
             g_means2D = None if stats is not None else (torch.empty((K, P, 3), **f32) if (_cap is None or "means2D" not in _cap)
                                                         else _cap["means2D"][:K])
-            g_colors = torch.empty((P, 3), **f32)
-            g_cov3D = torch.empty((P, 6), **f32)
-            g_view, g_proj = torch.empty((K, 4, 4), **f32), torch.empty((K, 4, 4), **f32)
-            scratch = torch.empty(L.dgs_backward_scratch_bytes(R, P, K), dtype=torch.uint8, device=dev)
-            io = _lib.DgsBackwardIO()
-            io.num_rendered = R
             depth_tv, g_depth = None, None
             if lambda_depth_tv > 0.0:
                 from . import losses as _losses
@@ -729,17 +665,14 @@ class FusedStep:
                 if shard is not None:
                     import torch.distributed as dist
                     dist.all_reduce(depth_tv, group=self.loss_group)   # the value only (logging); the gradient is local
-            io.radii, io.dL_dout_color, io.dL_dout_depth = ctypes.c_void_p(radii.data_ptr()), _ptr(dsub), _ptr(g_depth)
-            io.scratch, io.scratch_bytes = ctypes.c_void_p(scratch.data_ptr()), scratch.numel()
-            io.dL_dmeans3D, io.dL_dmeans2D, io.dL_dsh = _ptr(g_xyz), _ptr(g_means2D), _ptr(g_dc)
-            io.dL_dsh_rest = _ptr(g_rest) if Mr > 0 else None
-            io.dL_dcolors, io.dL_dopacity, io.dL_dscales, io.dL_drotations = _ptr(g_colors), _ptr(g_op), _ptr(g_sc), _ptr(g_rot)
-            io.dL_dcov3D, io.dL_dviewmatrix, io.dL_dprojmatrix = _ptr(g_cov3D), _ptr(g_view), _ptr(g_proj)
-            # sharded: the ranks' gradients are summed, so the hinge term is added by one of them only
-            io.opacity_hinge_scale = self.lambda_hinge / max(P, 1) if (shard is None or int(shard[0]) == 0) else 0.0
-            if stats is not None:
-                io.stats_max_radii2D, io.stats_grad_accum, io.stats_denom = (_ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]))
-                io.stats_K_total = int(K_total)
+            io, own = raster_call.backward_io(
+                R, radii, dsub, g_depth, means3D=g_xyz, means2D=g_means2D, sh=g_dc, sh_rest=g_rest if Mr > 0 else None,
+                opacity=g_op, scales=g_sc, rotations=g_rot,
+                # sharded: the ranks' gradients are summed, so the hinge term is added by one of them only
+                opacity_hinge_scale=self.lambda_hinge / max(P, 1) if (shard is None or int(shard[0]) == 0) else 0.0,
+                stats=stats, stats_K_total=K_total)
+            scratch, g_colors, g_cov3D = own["scratch"], own["colors"], own["cov3D"]
+            g_view, g_proj = own["viewmatrix"], own["projmatrix"]
             # ---- the launches up to the first collective ...
             chunked = not (ar is None or int(ar.get("chunks", 1)) <= 1 or P < 512)
             if chunked:
@@ -770,7 +703,6 @@ class FusedStep:
                         self._side = torch.cuda.Stream(device=dev)
                     side = self._side
                     flat.record_stream(side)
-                    widths = [3, 3, 3 * Mr, 1, 3, 4]
                     t_ar = None
                     if self.time_allreduce:  # (bench.py: span of the side stream's reductions, first chunk ready -> last done)
                         t_ar = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -783,8 +715,8 @@ class FusedStep:
                             side.wait_event(ev)
                             if t_ar is not None and ci == 0:
                                 t_ar[0].record(side)
-                            sharding.allreduce_slices([flat[offs[i] + b0 * c:offs[i] + b1 * c] for i, c in enumerate(widths)],
-                                                      ar.get("average", False), ar.get("group"))
+                            sharding.allreduce_slices(bucket.chunk(flat, P, b0, b1), ar.get("average", False),
+                                                      ar.get("group"))
                     _lib.check(L.dgs_backward_pose(ctypes.byref(prob), ctypes.byref(io), stream), "dgs_backward_pose")
                     done = torch.cuda.Event()
                     done.record(side)
@@ -809,7 +741,7 @@ class FusedStep:
                     pscratch = torch.empty(L.dgs_pose_scratch_bytes(K), dtype=torch.uint8, device=dev)
                     _lib.check(L.dgs_pose_backward(_ptr(ct_all, row), _ptr(cr_all, rrow), _ptr(nu_loc), _ptr(proj), C, K, quat,
                                                    _ptr(g_view),
-                                                   _ptr(g_proj), ctypes.c_void_p(pscratch.data_ptr()), _ptr(d_ct_all, row),
+                                                   _ptr(g_proj), _ptr(pscratch), _ptr(d_ct_all, row),
                                                    _ptr(d_cr_all, rrow), _ptr(d_nu), stream), "dgs_pose_backward")
                     m._trans._control_points.grad, m._rot._control_points.grad = d_ct_all, d_cr_all
                     if nrow > 0:

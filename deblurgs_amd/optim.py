@@ -14,12 +14,9 @@ import ctypes
 import torch
 
 from . import _lib
+from .raster_call import _stream
 
 FIELDS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")   # group names of the reference
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -28,6 +28,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .raster_call import Bucket
+
 
 # DGS_DIST_FORCE_COLLECTIVES=1: issue every collective of the product path even in a one-rank group (values unchanged).
 # tools/rccl_smoke.py uses it to put the real RCCL library, init path and reduction ops under a TrainingLoop step on a
@@ -99,11 +101,7 @@ def _adopt_into_bucket(params):
     if any(g is None or g.dtype != torch.float32 or not g.is_contiguous() for g in grads):
         return None
     st = grads[0].untyped_storage()
-    off = grads[0].storage_offset()
-    slots = []
-    for g in grads:
-        slots.append(off)
-        off += (g.numel() + 3) // 4 * 4
+    slots = [grads[0].storage_offset() + o for o in Bucket([g.numel() for g in grads]).offsets]
     last_end = slots[-1] + grads[-1].numel()      # the operator does not pad after the final segment
     if st.nbytes() < 4 * last_end:
         return None
@@ -406,19 +404,17 @@ def flat_allreduce_grads(params, average=False, group=None, extra=None, force=Fa
             shared = _adopt_into_bucket(params)
     if shared is not None:
         flat = shared
-    else:   # pack, every segment starting on a 16-byte boundary (the fused optimiser reads float4)
-        offs, total = [], 0
-        for g in grads:
-            offs.append(total)
-            total += (g.numel() + 3) // 4 * 4
-        flat = torch.zeros(total, dtype=torch.float32, device=grads[0].device)
-        for g, o in zip(grads, offs):
-            flat[o:o + g.numel()].copy_(g.reshape(-1))
+    else:   # pack into the fused operator's bucket layout (every segment on a 16-byte boundary)
+        bucket = Bucket([g.numel() for g in grads])
+        flat = torch.zeros(bucket.size, dtype=torch.float32, device=grads[0].device)
+        segs = bucket.views(flat, [g.shape for g in grads])
+        for g, v in zip(grads, segs):
+            v.copy_(g)
     _allreduce(flat, average, group)
     if shared is not None:
         return
-    for p, g, o in zip(params, grads, offs):
-        p.grad = flat[o:o + g.numel()].view_as(g).to(g.dtype)
+    for p, g, v in zip(params, grads, segs):
+        p.grad = v.to(g.dtype)
 
 
 def allreduce_densification_stats(cloud, prev, group=None):

@@ -1421,7 +1421,7 @@ def test_forward_only_path_is_bit_identical_and_keeps_no_backward_state(gpu):
     import ctypes
     import torch
     from helpers import _t, hip_settings
-    from deblurgs_amd import _lib
+    from deblurgs_amd import _lib, raster_call
     from deblurgs_amd import diff_gaussian_rasterization as dgr
     sc = small_scene(P=2500, W=176, H=120, K=3, seed=8)
     P, K = sc["P"], 3
@@ -1457,9 +1457,9 @@ def test_forward_only_path_is_bit_identical_and_keeps_no_backward_state(gpu):
         K, m3, sh, None, opc.reshape(-1), scc, rotc, None, view, proj, _t(sc["campos"][:K]), rsK, forward_only=True)
     torch.cuda.synchronize()
     assert image.numel() == small and torch.equal(color, outs[True][0]) and torch.equal(radii, outs[True][2])
-    prob = dgr._make_problem(K, m3, sh, None, opc.reshape(-1), scc, rotc, None, view, proj, _t(sc["campos"][:K]),
-                             dgr._RS(rsK, m3.device), geom, image, binning, getattr(R, "tile_cull", False))
-    prob.forward_only = 1
+    prob = raster_call.problem(K, m3, sh, None, opc.reshape(-1), scc, rotc, None, view, proj, _t(sc["campos"][:K]), rsK,
+                               dgr._bg(rsK, m3.device), getattr(R, "tile_cull", False), dgr.WIDE_RECORDS,
+                               forward_only=True, geom=geom, image=image, binning=binning)
     io = _lib.DgsBackwardIO()
     rc = L.dgs_backward(ctypes.byref(prob), ctypes.byref(io), None)
     assert rc == -1 and b"forward_only" in L.dgs_last_error()

@@ -111,25 +111,33 @@ def _worker_views(rank, world, port, out):
     if rank == 0:
         torch.save([p.grad.clone() for p in params], out)
     # the same gradients laid out as views of one padded flat buffer (what the fused-activation operator returns)
-    # must be reduced in place, without re-binding .grad
-    torch.manual_seed(200 + rank)
-    flat = torch.full((64 + 4 + 8,), float("nan"))
-    views = [flat[0:60].view(20, 3), flat[64:71]]
-    for v_, p in zip(views, params):
-        v_.copy_(torch.randn_like(p))
-    mine = [v_.clone() for v_ in views]
-    for v_, p in zip(views, params):
-        p.grad = v_
-    keep = [p.grad for p in params]
-    sharding.flat_allreduce_grads(params, average=True)
-    assert all(p.grad is k for p, k in zip(params, keep)), "shared-storage gradients must be reduced in place"
-    assert sharding._shared_flat(keep) is not None
-    gathered = [torch.zeros_like(m) for m in mine]
-    for g_, m in zip(gathered, mine):
-        g_.copy_(m)
-        dist.all_reduce(g_)
-        g_ /= world
-    assert all(torch.allclose(p.grad, g_, atol=1e-7) for p, g_ in zip(params, gathered))
+    # must be reduced in place, without re-binding .grad -- a buffer padded by hand, and one in the operator's own layout
+    from deblurgs_amd.raster_call import Bucket
+    bucket = Bucket([p.numel() for p in params])
+    assert bucket.offsets == [0, 60] and bucket.size == 68      # segments start on 16-byte boundaries
+    for layout in ("by hand", "bucket"):
+        torch.manual_seed(200 + rank)
+        if layout == "by hand":
+            flat = torch.full((64 + 4 + 8,), float("nan"))
+            views = [flat[0:60].view(20, 3), flat[64:71]]
+        else:
+            flat = torch.full((bucket.size,), float("nan"))
+            views = bucket.views(flat, [p.shape for p in params])
+        for v_, p in zip(views, params):
+            v_.copy_(torch.randn_like(p))
+        mine = [v_.clone() for v_ in views]
+        for v_, p in zip(views, params):
+            p.grad = v_
+        keep = [p.grad for p in params]
+        sharding.flat_allreduce_grads(params, average=True)
+        assert all(p.grad is k for p, k in zip(params, keep)), "shared-storage gradients must be reduced in place"
+        assert sharding._shared_flat(keep) is not None
+        gathered = [torch.zeros_like(m) for m in mine]
+        for g_, m in zip(gathered, mine):
+            g_.copy_(m)
+            dist.all_reduce(g_)
+            g_ /= world
+        assert all(torch.allclose(p.grad, g_, atol=1e-7) for p, g_ in zip(params, gathered))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -395,6 +403,29 @@ def test_poll_charges_every_overflow_to_its_own_step():
     assert fs.dropped == 2 and fs.retry == [("B", "all"), ("B", "all")]
     assert fs._seen[("A", 5, 0)] == [100, 101, 102] and fs._seen[("B", 5, 0)] == [900, 901]
     assert not fs._pending and len(fs._free_hosts) == 5
+
+
+def test_eager_is_faster_asks_the_context_of_the_clouds_device(monkeypatch):
+    """FusedStep._eager_is_faster predicts how the step's backward will be split, and that backward runs with
+    the package's context of the CLOUD's device (DgsProblem.context) -- not with the current device's.  Host side only:
+    _lib.context and the library are stubbed."""
+    import ctypes
+    import types
+    from deblurgs_amd import _lib
+    from deblurgs_amd.fused_step import FusedStep
+
+    class Cloud:
+        fused_activations = True
+        _xyz = types.SimpleNamespace(device=torch.device("cuda", 3))
+
+    handle, asked, parts = ctypes.c_void_p(0x5150), [], []
+    monkeypatch.setattr(_lib, "context", lambda device=None: asked.append(device) or handle)
+    monkeypatch.setattr(_lib, "lib", lambda: types.SimpleNamespace(
+        dgs_backward_parts=lambda ctx, K, cap, cull: parts.append(ctx) or 2))
+    fs = FusedStep(Cloud(), motion=None)
+    assert fs._eager_is_faster(12, 1 << 20, True) and fs.eager_preferred == 1
+    assert asked and all(d == 3 for d in asked), asked
+    assert parts == [handle]
 
 
 def test_rccl_log_parser_reads_version_algorithm_and_topology(tmp_path):
