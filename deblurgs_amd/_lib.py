@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DGS_LIB_PATH") or os.path.join(_HERE, "libdgs_hip.so")
 
 DGS_MAX_K = 128
+TONE_IDENTITY, TONE_GAMMA = 0, 1       # DGS_TONE_* of dgs_view_loss_grad
 STAGES = ["preprocess", "scan", "duplicate", "sort", "ranges", "composite_fwd", "composite_bwd", "geometry_bwd",
           "depth_order", "tile_cull", "contrib_reduce"]
 
@@ -90,7 +91,7 @@ class DgsCloudArrays(ctypes.Structure):
 
 
 ADAM_MAX_GROUPS = 16
-ABI_VERSION = 14           # DGS_ABI_VERSION of include/dgs_hip.h (tests/test_abi.py keeps the two in step)
+ABI_VERSION = 15           # DGS_ABI_VERSION of include/dgs_hip.h (tests/test_abi.py keeps the two in step)
 
 # every symbol include/dgs_hip.h declares (tests check that the library exports exactly these)
 EXPORTS = {
@@ -179,6 +180,15 @@ EXPORTS = {
     "dgs_pose_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
     "dgs_pose_forward": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4),
     "dgs_pose_backward": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 7),
+    "dgs_backward_pose_only": (ctypes.c_int, [ctypes.POINTER(DgsProblem), ctypes.POINTER(DgsBackwardIO),
+                                              ctypes.c_void_p]),
+    "dgs_testpose_forward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 5),
+    "dgs_testpose_backward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 6),
+    "dgs_view_loss_grad": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 4 + [ctypes.c_float] * 2 +
+                           [ctypes.c_void_p] * 6),
+    "dgs_image_metrics_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
+    "dgs_image_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

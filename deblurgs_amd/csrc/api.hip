@@ -1033,6 +1033,54 @@ int dgs_backward_pose(const DgsProblem* p, const DgsBackwardIO* io, dgs_stream_t
   return backward_impl(p, io, 4, 0, 0, reinterpret_cast<hipStream_t>(stream));
 }
 
+// The backward of a caller that optimises the CAMERA only (the test-view pose fit, test.py:131-186): the compositing
+// backward and the per-pair totals as dgs_backward runs them, then geometry_pose_bwd_kernel instead of the per-Gaussian
+// kernel.  Always one launch chain on `s`: the context's side stream is never used.
+int dgs_backward_pose_only(const DgsProblem* p, const DgsBackwardIO* io, dgs_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int rc = check_problem(p, p != nullptr && p->raw_params != 0);
+  if (rc != DGS_OK) return rc;
+  if (p->forward_only)
+    return fail(DGS_E_ARG, "backward_pose_only: the problem is forward_only (nothing was kept for a backward)");
+  if (io == nullptr) return fail(DGS_E_ARG, "null DgsBackwardIO");
+  if (io->dL_dviewmatrix == nullptr || io->dL_dprojmatrix == nullptr)
+    return fail(DGS_E_ARG, "dL_dviewmatrix / dL_dprojmatrix are null");
+  if (p->P == 0) {
+    hipError_t e = hipMemsetAsync(io->dL_dviewmatrix, 0, (size_t)p->K * 64, s);
+    if (e == hipSuccess) e = hipMemsetAsync(io->dL_dprojmatrix, 0, (size_t)p->K * 64, s);
+    return e == hipSuccess ? DGS_OK : fail_hip(e, "memset grads");
+  }
+  if (io->dL_dout_color == nullptr || io->radii == nullptr)
+    return fail(DGS_E_ARG, "DgsBackwardIO: dL_dout_color / radii are null");
+  const uint64_t R = io->num_rendered;
+  DgsLayout L;
+  make_layout(p->P, p->W, p->H, p->K, R, p->wide_records != 0, &L);
+  if (p->geom_state == nullptr || p->geom_bytes < L.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
+  if (p->image_state == nullptr || p->image_bytes < L.image_total) return fail(DGS_E_CAPACITY, "image_state too small");
+  if (R > 0 && (p->binning_state == nullptr || p->binning_bytes < L.binning_total))
+    return fail(DGS_E_CAPACITY, "binning_state too small");
+  if (io->scratch == nullptr || io->scratch_bytes < dgs_backward_scratch_bytes(R, p->P, p->K))
+    return fail(DGS_E_CAPACITY, "backward scratch too small");
+  DgsCarve c;
+  carve(p, L, &c);
+  DgsView v = make_view(p);
+  if (v.tile_cull) {
+    v.pack_g_shift = L.pack_g_shift;
+    v.pack_tile_shift = L.pack_tile_shift;
+  }
+  float* contrib = reinterpret_cast<float*>(io->scratch);
+  float* sums = reinterpret_cast<float*>(reinterpret_cast<char*>(io->scratch) + up((size_t)R * DGS_CONTRIB_F * 4));
+  double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(sums) +
+                                               up((size_t)p->K * (size_t)p->P * DGS_SUMS_F * 4));
+  DGS_STAGE(DGS_STAGE_COMPOSITE_BWD, "composite backward",
+            dgs_launch_composite_bwd(v, c, p->bg, io->dL_dout_color, io->dL_dout_depth, contrib, s, 0, -1, true));
+  DGS_STAGE(DGS_STAGE_CONTRIB_REDUCE, "contribution-row totals",
+            dgs_launch_geometry_pose_bwd(*p, v, c, *io, contrib, sums, partials, s, 1));
+  DGS_STAGE(DGS_STAGE_GEOMETRY_BWD, "geometry backward (pose only)",
+            dgs_launch_geometry_pose_bwd(*p, v, c, *io, contrib, sums, partials, s, 2));
+  return DGS_OK;
+}
+
 int dgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, dgs_stream_t stream) {
   (void)projmatrix;  // in_frustum only uses the view depth (auxiliary.h:159)

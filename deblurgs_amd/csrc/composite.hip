@@ -310,8 +310,13 @@ composite_fwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ rang
 
 // ----------------------------------------------------------------------------------------------- backward
 // TIGHT: the duplicate index travels in the low key word (tile_cull emission).  HASDEPTH: dL_ddepth is given (the
-// default training loss does not use the depth output: the depth channel then drops out of the per-pair math)
-template <bool TIGHT, bool HASDEPTH>
+// default training loss does not use the depth output: the depth channel then drops out of the per-pair math).
+// POSE: the caller wants the camera gradients alone (dgs_backward_pose_only).  Colour does not depend on the pose in this
+// fork, so the colour sums sA, sB.x and the weight sum S_w are dead: they are neither accumulated nor reduced nor stored.
+// accg, `behind`, the T recurrence and every per-pair decision are untouched.  The contribution row is then
+// [S_wx, S_wy, S_xx, S_xy, S_yy, depth, 0, 0]: eight columns, all written as values (the depth column and the two pad
+// columns are zeros where nothing feeds them), which contrib_reduce_kernel<2> and geometry_pose_bwd_kernel read.
+template <bool TIGHT, bool HASDEPTH, bool POSE = false>
 __global__ void __launch_bounds__(64 * CW)
 composite_bwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ ranges,
                      const uint32_t* __restrict__ point_list, const uint64_t* __restrict__ keys,
@@ -340,7 +345,7 @@ composite_bwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ rang
   // reduction through LDS: lane (row = lane >> 2, quarter = lane & 3), row < 10 (9 without a depth gradient), sums 16 lanes'
   // values of sum `row`; the quad's four partial sums are combined with two DPP adds and lane quarter 0 stores the total
   const int rrow = lane >> 2, rq = lane & 3;
-  const bool rlane = rrow < (HASDEPTH ? 10 : 9);
+  const bool rlane = rrow < (POSE ? (HASDEPTH ? 6 : 5) : (HASDEPTH ? 10 : 9));
   float* const contrib_lane = contrib + (rrow < 10 ? rrow : 0);   // this lane's column of every contribution row
   static_assert(sizeof(float) * 68 == 272, "the store offsets below are multiples of one s_part row");
   // LDS byte offset of this wave's s_part block (the low half of a flat LDS address is the offset inside the LDS)
@@ -448,7 +453,7 @@ composite_bwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ rang
       float4* dst = reinterpret_cast<float4*>(contrib + (size_t)u * DGS_CONTRIB_F);
       dst[0] = z4;
       dst[1] = z4;
-      dst[2] = z4;
+      if (!POSE) dst[2] = z4;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -534,11 +539,13 @@ composite_bwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ rang
           const float wgt = au * (behind * T[q]);  // au == 0 for a skipped pair
           const float wx = wgt * dx, wy = wgt * dy;
           // (scalar FMAs: a packed v_pk_fma_f32 was measured slower than the two scalar ones it replaces)
-          sA.x = fmaf(gA[q].x, dchannel_dcolor, sA.x);
-          sA.y = fmaf(gA[q].y, dchannel_dcolor, sA.y);
-          sB.x = fmaf(gB[q].x, dchannel_dcolor, sB.x);
+          if (!POSE) {
+            sA.x = fmaf(gA[q].x, dchannel_dcolor, sA.x);
+            sA.y = fmaf(gA[q].y, dchannel_dcolor, sA.y);
+            sB.x = fmaf(gB[q].x, dchannel_dcolor, sB.x);
+          }
           if (HASDEPTH) sB.y = fmaf(gB[q].y, dchannel_dcolor, sB.y);
-          S_w += wgt;
+          if (!POSE) S_w += wgt;
           S_wx += wx;
           S_wy += wy;
           S_xx = fmaf(wx, dx, S_xx);
@@ -568,7 +575,21 @@ composite_bwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ rang
         // write of M0 needs one wait state before an add-TID LDS instruction reads it -- the compiler inserts that for its
         // own code, not inside asm; without it the stores of some waves went to a stale M0 (tools/addtid_probe.hip).
         // A wave's LDS operations execute in order, so the loads below see these stores without a wait.
-        if (HASDEPTH)
+        if (POSE && HASDEPTH)
+          asm volatile(
+              "s_mov_b32 m0, %6\n\ts_nop 0\n\t"
+              "ds_write_addtid_b32 %0 offset:0\n\tds_write_addtid_b32 %1 offset:272\n\t"
+              "ds_write_addtid_b32 %2 offset:544\n\tds_write_addtid_b32 %3 offset:816\n\t"
+              "ds_write_addtid_b32 %4 offset:1088\n\tds_write_addtid_b32 %5 offset:1360"
+              :: "v"(S_wx), "v"(S_wy), "v"(S_xx), "v"(S_xy), "v"(S_yy), "v"(sB.y), "s"(part_base) : "m0", "memory");
+        else if (POSE)
+          asm volatile(
+              "s_mov_b32 m0, %5\n\ts_nop 0\n\t"
+              "ds_write_addtid_b32 %0 offset:0\n\tds_write_addtid_b32 %1 offset:272\n\t"
+              "ds_write_addtid_b32 %2 offset:544\n\tds_write_addtid_b32 %3 offset:816\n\t"
+              "ds_write_addtid_b32 %4 offset:1088"
+              :: "v"(S_wx), "v"(S_wy), "v"(S_xx), "v"(S_xy), "v"(S_yy), "s"(part_base) : "m0", "memory");
+        else if (HASDEPTH)
           asm volatile(
               "s_mov_b32 m0, %10\n\ts_nop 0\n\t"
               "ds_write_addtid_b32 %0 offset:0\n\tds_write_addtid_b32 %1 offset:272\n\t"
@@ -607,7 +628,8 @@ composite_bwd_kernel(DgsView v, uint32_t per_xcd, const uint2* __restrict__ rang
           // multiplies, add with carry, global_store with a scalar base -- measured the same: 5.41 / 5.45 ms.)  Without a
           // depth gradient the lanes of column 9 read nothing and store the 0 they started from; columns 10 and 11 of a
           // row are never read as values.
-          if (rrow < 10 && rq == 0) contrib_lane[(size_t)uj * DGS_CONTRIB_F] = tot;
+          // POSE: eight columns, the lanes of the columns nothing feeds store the 0 they started from
+          if (rrow < (POSE ? 8 : 10) && rq == 0) contrib_lane[(size_t)uj * DGS_CONTRIB_F] = tot;
         }
         __builtin_amdgcn_wave_barrier();   // the next entry's stores follow this entry's loads (LDS runs a wave's ops in order)
       }
@@ -675,7 +697,7 @@ hipError_t dgs_launch_composite_fwd(const DgsView& v, const DgsCarve& c, const f
 }
 
 hipError_t dgs_launch_composite_bwd(const DgsView& v_all, const DgsCarve& c, const float* bg, const float* dL_dpix,
-                                    const float* dL_ddepth, float* contrib, hipStream_t s, int k0, int k1) {
+                                    const float* dL_ddepth, float* contrib, hipStream_t s, int k0, int k1, bool pose) {
   // subframes [k0, k1) of the view (k1 < 0: all of them): the kernel sees a view of k1 - k0 subframes whose per-subframe
   // arrays start at subframe k0; list positions (ranges, keys, duplicate offsets, contribution rows) are absolute
   if (k1 < 0) { k0 = 0; k1 = v_all.K; }
@@ -690,10 +712,16 @@ hipError_t dgs_launch_composite_bwd(const DgsView& v_all, const DgsCarve& c, con
   const uint32_t* n_contrib = c.n_contrib + (size_t)k0 * N;
   dL_dpix += (size_t)k0 * 3 * N;
   if (dL_ddepth != nullptr) dL_ddepth += (size_t)k0 * N;
-#define DGS_CBWD(TI, HD)                                                                                            \
-  hipLaunchKernelGGL((composite_bwd_kernel<TI, HD>), dim3(per * 8), dim3(64 * CW), 0, s, v, per, ranges, c.point_list, \
+#define DGS_CBWD(TI, HD, ...)                                                                                       \
+  hipLaunchKernelGGL((composite_bwd_kernel<TI, HD, ##__VA_ARGS__>), dim3(per * 8), dim3(64 * CW), 0, s, v, per, ranges, c.point_list, \
                      c.keys_sorted, rows, bg, final_T, n_contrib, dL_dpix, dL_ddepth, c.point_offsets, contrib)
-  if (v.tile_cull) {
+  if (pose) {   // the camera gradients alone: no colour sums (dgs_backward_pose_only)
+    if (v.tile_cull) {
+      if (dL_ddepth != nullptr) DGS_CBWD(true, true, true); else DGS_CBWD(true, false, true);
+    } else {
+      if (dL_ddepth != nullptr) DGS_CBWD(false, true, true); else DGS_CBWD(false, false, true);
+    }
+  } else if (v.tile_cull) {
     if (dL_ddepth != nullptr) DGS_CBWD(true, true); else DGS_CBWD(true, false);
   } else {
     if (dL_ddepth != nullptr) DGS_CBWD(false, true); else DGS_CBWD(false, false);

@@ -61,6 +61,9 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // (Round 3 tried a streaming variant -- a wave owns 64 consecutive pairs and pulls their contiguous row span through LDS
 // with fully coalesced 1 KB loads -- and measured the same time, 0.82 vs 0.80 ms: the kernel is bound by the 11.8 M
 // scattered 48-byte WRITES of the totals to their natural index, not by how the rows are read.)
+// NPARTS = float4 parts of a row that hold values: 3 (the ten sums), or 2 for the eight-column rows of the pose-only
+// compositing instantiation (parts 2 and 3 then neither read nor write anything)
+template <int NPARTS = 3>
 __global__ void __launch_bounds__(256)
 contrib_reduce_kernel(uint64_t n, const uint32_t* __restrict__ status, const uint32_t* __restrict__ order,
                       const uint32_t* __restrict__ tt_visible, const uint32_t* __restrict__ tiles,
@@ -74,11 +77,12 @@ contrib_reduce_kernel(uint64_t n, const uint32_t* __restrict__ status, const uin
   const uint64_t j = t >> 2;
   const uint32_t part = (uint32_t)t & 3u;
   if (j >= n || (part == 3u && DGS_SUMS_F < 16)) return;
+  if (NPARTS < 3 && part >= (uint32_t)NPARTS) return;
   // the four index words are requested together (one round trip instead of a chain of three) ...
   const uint32_t vis = tt_visible[j], nt = tiles[j], off = offsets[j], dst = order[j];
   if (vis == 0u) return;  // invisible pair: the geometry kernel never reads its slot
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (nt > 0 && part < 3u) {
+  if (nt > 0 && part < (uint32_t)NPARTS) {
     const float4* cp = reinterpret_cast<const float4*>(contrib + (size_t)off * DGS_CONTRIB_F) + part;
     // ... and so are the first four rows of the segment (a pair has ~3 duplicates on average), then eight at a time:
     // the loop is never a chain of dependent HBM round trips.  Rows are added strictly in duplicate order, one after the
@@ -703,6 +707,192 @@ geometry_bwd_kernel(DgsView v, const float* __restrict__ means3D, const float* _
   }
 }
 
+// Pose-only sibling of geometry_bwd_kernel (dgs_backward_pose_only: the test-view pose fit, test.py:131-186, asks for the
+// two camera matrices' gradients and nothing else).  One thread per Gaussian walks the K subframes and keeps what
+// dL_dviewmatrix / dL_dprojmatrix need -- the per-pair totals S_wx, S_wy, S_xx, S_xy, S_yy and the depth total, the stored
+// cov3D, the row, the two matrices, the conic -> cov2D -> dL_dt chain and the dL_dmean2D -> projection-matrix terms in
+// double -- with every expression written as geometry_bwd_kernel writes it.  No SH loads or SH backward, no cov3D ->
+// scale / rotation, no opacity or colour sums, no per-Gaussian stores, no statistics.  Same per-block partials layout, same
+// pose_grad_reduce_kernel behind it: deterministic.
+// The totals come from the eight-column rows of composite_bwd_kernel<.., .., POSE>: depth total in column 5.
+__global__ void __launch_bounds__(GB_THREADS)
+geometry_pose_bwd_kernel(DgsView v, const float* __restrict__ means3D, const float* __restrict__ cov3D_precomp,
+                         const float* __restrict__ viewm, const float* __restrict__ projm,
+                         const DgsRow* __restrict__ rows, const float* __restrict__ cov3Ds,
+                         const uint32_t* __restrict__ tiles_touched, const float* __restrict__ contrib,
+                         const uint32_t* __restrict__ status, double* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) float s_part[];  // [waves][K][NMAT]
+  __shared__ __attribute__((aligned(16))) float s_m[GB_THREADS / 64][21][68];  // one subframe's 21 pose terms of every lane
+  if (status[5] != 0u) return;  // capacity mode, truncated lists (see contrib_reduce_kernel); the caller discards the step
+  const int idx = blockIdx.x * GB_THREADS + threadIdx.x;
+  const bool valid = idx < v.P;
+  const int gi = valid ? idx : 0;
+  const int lane = dgs_lane(), w = threadIdx.x >> 6;
+  const float mx = means3D[3 * gi], my = means3D[3 * gi + 1], mz = means3D[3 * gi + 2];
+  const float* c3p = (cov3D_precomp != nullptr ? cov3D_precomp : cov3Ds) + 6 * (size_t)gi;
+  float c3[6];
+#pragma unroll
+  for (int i = 0; i < 6; i++) c3[i] = c3p[i];
+  const float h_x = v.focal_x, h_y = v.focal_y;
+
+  // the loads of subframe k + 1 -- tiles_touched, the first two quarters of the row, the total at the natural index --
+  // are issued before subframe k computes
+  struct Pf {
+    uint32_t nt;
+    float4 ga, gb;  // x, y, cx, cy | cz, op, r, g
+    float4 r0, r1;
+  };
+  auto load_pf = [&](int k) {
+    Pf f;
+    const size_t o = (size_t)k * v.P + gi;
+    const float4* rowp = reinterpret_cast<const float4*>(rows + o);
+    f.nt = valid ? tiles_touched[o] : 0u;
+    f.ga = rowp[0];   // unconditional (no dependent hop); rows and totals of invisible pairs are never used
+    f.gb = rowp[1];
+    const float4* cp = reinterpret_cast<const float4*>(contrib + o * DGS_SUMS_F);
+    f.r0 = cp[0];
+    f.r1 = cp[1];
+    return f;
+  };
+  Pf nxt = load_pf(0);
+
+  for (int k = 0; k < v.K; k++) {
+    const float* V = viewm + 16 * k;
+    const float* F = projm + 16 * k;
+    float mat[NMAT];
+#pragma unroll
+    for (int i = 0; i < NMAT; i++) mat[i] = 0.0f;
+    float g2x = 0.0f, g2y = 0.0f;
+    const Pf cur = nxt;
+    if (k + 1 < v.K) nxt = load_pf(k + 1);
+    const uint32_t ntiles = cur.nt;
+    if (ntiles > 0) {
+      const float4 ga = cur.ga, gb = cur.gb;
+      const float4 r0 = cur.r0, r1 = cur.r1;
+      const float s[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y};
+      g2x = -(0.5f * (float)v.W) * (ga.z * s[0] + ga.w * s[1]);
+      g2y = -(0.5f * (float)v.H) * (gb.x * s[1] + ga.w * s[0]);
+      const float dcon_x = -0.5f * s[2], dcon_y = -0.5f * s[3], dcon_w = -0.5f * s[4];
+      const float ddepth = s[5];
+
+      // ---- computeCov2DCUDA (backward.cu:145-295)
+      float tx = V[0] * mx + V[4] * my + V[8] * mz + V[12];
+      float ty = V[1] * mx + V[5] * my + V[9] * mz + V[13];
+      const float tz_ = V[2] * mx + V[6] * my + V[10] * mz + V[14];
+      const float limx = 1.3f * v.tanfovx, limy = 1.3f * v.tanfovy;
+      const float txtz = tx / tz_, tytz = ty / tz_;
+      tx = fminf(limx, fmaxf(-limx, txtz)) * tz_;
+      ty = fminf(limy, fmaxf(-limy, tytz)) * tz_;
+      const float x_grad_mul = (txtz < -limx || txtz > limx) ? 0.0f : 1.0f;
+      const float y_grad_mul = (tytz < -limy || tytz > limy) ? 0.0f : 1.0f;
+      M3 J = {{{h_x / tz_, 0.0f, -(h_x * tx) / (tz_ * tz_)}, {0.0f, h_y / tz_, -(h_y * ty) / (tz_ * tz_)}, {0, 0, 0}}};
+      M3 Wm = {{{V[0], V[4], V[8]}, {V[1], V[5], V[9]}, {V[2], V[6], V[10]}}};
+      M3 Vrk = {{{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}}};
+      M3 T = mul(Wm, J);
+      M3 cov2D = mul(mul(tr(T), tr(Vrk)), T);
+      const float a = cov2D.m[0][0] + 0.3f;
+      const float b = cov2D.m[0][1];
+      const float c = cov2D.m[1][1] + 0.3f;
+      const float denom = a * c - b * b;
+      float dL_da = 0, dL_db = 0, dL_dc = 0;
+      const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+      if (denom2inv != 0) {
+        dL_da = denom2inv * (-c * c * dcon_x + 2 * b * c * dcon_y + (denom - a * c) * dcon_w);
+        dL_dc = denom2inv * (-a * a * dcon_w + 2 * a * b * dcon_y + (denom - a * c) * dcon_x);
+        dL_db = denom2inv * 2 * (b * c * dcon_x - (denom + 2 * b * b) * dcon_y + a * b * dcon_w);
+      }
+      const float dL_dT00 = 2 * (T.m[0][0] * Vrk.m[0][0] + T.m[0][1] * Vrk.m[0][1] + T.m[0][2] * Vrk.m[0][2]) * dL_da +
+                            (T.m[1][0] * Vrk.m[0][0] + T.m[1][1] * Vrk.m[0][1] + T.m[1][2] * Vrk.m[0][2]) * dL_db;
+      const float dL_dT01 = 2 * (T.m[0][0] * Vrk.m[1][0] + T.m[0][1] * Vrk.m[1][1] + T.m[0][2] * Vrk.m[1][2]) * dL_da +
+                            (T.m[1][0] * Vrk.m[1][0] + T.m[1][1] * Vrk.m[1][1] + T.m[1][2] * Vrk.m[1][2]) * dL_db;
+      const float dL_dT02 = 2 * (T.m[0][0] * Vrk.m[2][0] + T.m[0][1] * Vrk.m[2][1] + T.m[0][2] * Vrk.m[2][2]) * dL_da +
+                            (T.m[1][0] * Vrk.m[2][0] + T.m[1][1] * Vrk.m[2][1] + T.m[1][2] * Vrk.m[2][2]) * dL_db;
+      const float dL_dT10 = 2 * (T.m[1][0] * Vrk.m[0][0] + T.m[1][1] * Vrk.m[0][1] + T.m[1][2] * Vrk.m[0][2]) * dL_dc +
+                            (T.m[0][0] * Vrk.m[0][0] + T.m[0][1] * Vrk.m[0][1] + T.m[0][2] * Vrk.m[0][2]) * dL_db;
+      const float dL_dT11 = 2 * (T.m[1][0] * Vrk.m[1][0] + T.m[1][1] * Vrk.m[1][1] + T.m[1][2] * Vrk.m[1][2]) * dL_dc +
+                            (T.m[0][0] * Vrk.m[1][0] + T.m[0][1] * Vrk.m[1][1] + T.m[0][2] * Vrk.m[1][2]) * dL_db;
+      const float dL_dT12 = 2 * (T.m[1][0] * Vrk.m[2][0] + T.m[1][1] * Vrk.m[2][1] + T.m[1][2] * Vrk.m[2][2]) * dL_dc +
+                            (T.m[0][0] * Vrk.m[2][0] + T.m[0][1] * Vrk.m[2][1] + T.m[0][2] * Vrk.m[2][2]) * dL_db;
+      const float dL_dJ00 = Wm.m[0][0] * dL_dT00 + Wm.m[0][1] * dL_dT01 + Wm.m[0][2] * dL_dT02;
+      const float dL_dJ02 = Wm.m[2][0] * dL_dT00 + Wm.m[2][1] * dL_dT01 + Wm.m[2][2] * dL_dT02;
+      const float dL_dJ11 = Wm.m[1][0] * dL_dT10 + Wm.m[1][1] * dL_dT11 + Wm.m[1][2] * dL_dT12;
+      const float dL_dJ12 = Wm.m[2][0] * dL_dT10 + Wm.m[2][1] * dL_dT11 + Wm.m[2][2] * dL_dT12;
+      const float tz = 1.f / tz_;
+      const float tz2 = tz * tz;
+      const float tz3 = tz2 * tz;
+      const float dL_dtx = x_grad_mul * -h_x * tz2 * dL_dJ02;
+      const float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
+      const float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * tx) * tz3 * dL_dJ02 +
+                           (2 * h_y * ty) * tz3 * dL_dJ12;
+      // view-matrix gradient through t = view * mean only (backward.cu:277-294) ...
+      mat[0] = dL_dtx * mx;  mat[1] = dL_dty * mx;  mat[2] = dL_dtz * mx;
+      mat[3] = dL_dtx * my;  mat[4] = dL_dty * my;  mat[5] = dL_dtz * my;
+      mat[6] = dL_dtx * mz;  mat[7] = dL_dty * mz;  mat[8] = dL_dtz * mz;
+      mat[9] = dL_dtx;       mat[10] = dL_dty;      mat[11] = dL_dtz;
+      // ... and through depth (backward.cu:454-457): view[2], [6], [10], [14]
+      mat[2] += ddepth * mx;
+      mat[5] += ddepth * my;
+      mat[8] += ddepth * mz;
+      mat[11] += ddepth;
+
+      // ---- preprocessCUDA backward (backward.cu:367-460), the projection-matrix terms alone
+      const float mhx = F[0] * mx + F[4] * my + F[8] * mz + F[12];
+      const float mhy = F[1] * mx + F[5] * my + F[9] * mz + F[13];
+      const float mhw = F[3] * mx + F[7] * my + F[11] * mz + F[15];
+      const float m_w = 1.0f / (mhw + 0.0000001f);
+      const float lastcol = (mhx * v.W * g2x + mhy * v.H * g2y) * m_w * m_w;
+      mat[12] = (float)(0.5 * g2x * mx * v.W * m_w);
+      mat[13] = (float)(0.5 * g2y * mx * v.H * m_w);
+      mat[14] = (float)(0.5 * g2x * my * v.W * m_w);
+      mat[15] = (float)(0.5 * g2y * my * v.H * m_w);
+      mat[16] = (float)(0.5 * g2x * mz * v.W * m_w);
+      mat[17] = (float)(0.5 * g2y * mz * v.H * m_w);
+      mat[18] = (float)(0.5 * g2x * v.W * m_w);
+      mat[19] = (float)(0.5 * g2y * v.H * m_w);
+      mat[20] = (float)(-0.5 * lastcol);
+    }
+    // ---- per-subframe pose gradients: the wave sum of geometry_bwd_kernel, operation for operation
+    {
+      float* sp = s_part + ((size_t)w * v.K + k) * NMAT;
+      if (__ballot(ntiles > 0) != 0ull) {
+        float* pw = &s_m[w][0][lane];
+#pragma unroll
+        for (int i = 0; i < 21; i++) pw[i * 68] = mat[i];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int rrow = lane >> 2, rq = lane & 3;
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+          const int row = rrow + 16 * half;
+          float tot = 0.0f;
+          if (row < 21) {
+            const float4* pr = reinterpret_cast<const float4*>(&s_m[w][row][16 * rq]);
+            const float4 x0 = pr[0], x1 = pr[1], x2 = pr[2], x3 = pr[3];
+            tot = (((x0.x + x0.y) + (x0.z + x0.w)) + ((x1.x + x1.y) + (x1.z + x1.w))) +
+                  (((x2.x + x2.y) + (x2.z + x2.w)) + ((x3.x + x3.y) + (x3.z + x3.w)));
+          }
+          tot = dgs_quad_sum(tot);
+          if (row < 21 && rq == 0) sp[row] = tot;
+        }
+        __builtin_amdgcn_wave_barrier();
+      } else if (lane < 21) {
+        sp[lane] = 0.0f;
+      }
+    }
+  }
+
+  // ---- the 4 waves in wave order, in double (see geometry_bwd_kernel)
+  __syncthreads();
+  const int total = v.K * NMAT;
+  for (int i = threadIdx.x; i < total; i += GB_THREADS) {
+    double acc = 0.0;
+#pragma unroll
+    for (int ww = 0; ww < GB_THREADS / 64; ww++) acc += (double)s_part[(size_t)ww * total + i];
+    partials[(size_t)blockIdx.x * total + i] = acc;
+  }
+}
+
 // Sums the per-block partials and scatters them into the two [K,4,4] outputs.  Deterministic: thread t adds
 // blocks t, t+256, ... in order for all 21 values at once (one 84-byte row per block), then a fixed-shape tree
 // over the 256 threads combines them.
@@ -772,7 +962,7 @@ hipError_t dgs_launch_geometry_bwd(const DgsProblem& p, const DgsView& v, const 
     if (k1 < 0) { k0 = 0; k1 = v.K; }
     const uint64_t j0 = (uint64_t)k0 * v.P, nj = (uint64_t)(k1 - k0) * v.P;
     if (nj > 0)
-      hipLaunchKernelGGL(contrib_reduce_kernel, dim3((uint32_t)((4 * nj + 255) / 256)), dim3(256), 0, s, nj, c.num_rendered,
+      hipLaunchKernelGGL(contrib_reduce_kernel<3>, dim3((uint32_t)((4 * nj + 255) / 256)), dim3(256), 0, s, nj, c.num_rendered,
                          c.gsort_vals + j0, c.tt_sorted + j0, (v.tile_cull ? c.tt_tight : c.tt_sorted) + j0,
                          (v.tile_cull ? c.offs_tight : c.offs_sorted) + j0, contrib, sums);
   }
@@ -804,5 +994,30 @@ hipError_t dgs_launch_geometry_bwd(const DgsProblem& p, const DgsView& v, const 
   if (phases & 4)
     hipLaunchKernelGGL(pose_grad_reduce_kernel, dim3(v.K), dim3(256), 0, s, v.K, all_blocks, partials, io.dL_dviewmatrix,
                        io.dL_dprojmatrix);
+  return hipGetLastError();
+}
+
+// dgs_backward_pose_only: the per-pair totals of all subframes, the pose-only per-Gaussian kernel over all Gaussians and the
+// final sum of its per-block partials -- one launch chain on `s`
+hipError_t dgs_launch_geometry_pose_bwd(const DgsProblem& p, const DgsView& v, const DgsCarve& c, const DgsBackwardIO& io,
+                                        const float* contrib, float* sums, double* partials, hipStream_t s, int phases) {
+  if ((phases & 1) && (io.num_rendered > 0 || v.tile_cull)) {
+    const uint64_t nj = (uint64_t)v.K * v.P;   // (as phase 1 of dgs_launch_geometry_bwd, two parts of every row)
+    if (nj > 0)
+      hipLaunchKernelGGL(contrib_reduce_kernel<2>, dim3((uint32_t)((4 * nj + 255) / 256)), dim3(256), 0, s, nj, c.num_rendered,
+                         c.gsort_vals, c.tt_sorted, v.tile_cull ? c.tt_tight : c.tt_sorted,
+                         v.tile_cull ? c.offs_tight : c.offs_sorted, contrib, sums);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (!(phases & 2)) return hipSuccess;
+  const int all_blocks = dgs_geometry_bwd_blocks(v.P);
+  const size_t lds = (size_t)(GB_THREADS / 64) * v.K * NMAT * sizeof(float);
+  hipLaunchKernelGGL(geometry_pose_bwd_kernel, dim3(all_blocks), dim3(GB_THREADS), lds, s, v, p.means3D, p.cov3D_precomp,
+                     p.viewmatrix, p.projmatrix, c.rows, c.cov3D, c.tiles_touched, sums, c.num_rendered, partials);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pose_grad_reduce_kernel, dim3(v.K), dim3(256), 0, s, v.K, all_blocks, partials, io.dL_dviewmatrix,
+                     io.dL_dprojmatrix);
   return hipGetLastError();
 }

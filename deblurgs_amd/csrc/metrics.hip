@@ -1,0 +1,274 @@
+// metrics.hip -- the image-space kernels of the evaluation protocol (test.py:93-186 of the reference):
+//   * dgs_view_loss_grad: the loss of one step of the test-view pose fit (test.py:171-178) -- tone mapping
+//     (scene/tonemapping.py), clamp to [0, 1], L1 against the test image -- with its value, the MSE of the reference's
+//     l2_error_ema and dL/d(render) in one pass;
+//   * dgs_image_metrics: PSNR (utils/image_utils.py:17-19) and SSIM (utils/loss_utils.py:23-63) of two [3,H,W] images in
+//     one launch plus a reduction.
+// Built with -ffp-contract=off (deblurgs_amd/build.py): the SSIM of an image with itself is exactly 1 only while
+// 2 (mu1 mu2) and mu1^2 + mu2^2 round the same way.
+// Every total is deterministic: per-block sums in a fixed order, then either integer (fixed-point) atomics or a second
+// kernel that adds the blocks in index order.
+#include <math.h>
+
+#include "dgs_common.h"
+
+extern int dgs_fail_arg(const char* msg);
+extern int dgs_fail_hip(hipError_t e, const char* where);
+
+namespace {
+
+__device__ __forceinline__ float sgnf(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
+
+// sum over the 256 threads of a block in a fixed order (lane order inside a wave, then wave order); valid in thread 0
+__device__ __forceinline__ double block_sum_256(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------- view loss
+// One element per thread and grid stride: y = clamp(tone_map(x), 0, 1), d = y - gt, l1 += |d|, mse += d^2,
+//   dL/dx = upstream * sign(d) / E * [0 <= tone_map(x) <= 1] * tone_map'(x)
+// with torch's conventions: clamp and clamp_min pass the gradient on the bound, sign(0) = 0.  gamma:
+//   tone_map(x) = max((x - bound) / (1 - 2 bound), eps) ^ (1 / 2.2)   (losses.ToneMapping)
+// and its derivative as torch's pow backward forms it: (1 / 2.2) u ^ (1 / 2.2 - 1), exponents rounded to fp32.
+// work: 12 words, zeroed by the launcher -- [0] l1, [1] mse (fp32), [2..3] / [4..5] 2^-24 fixed-point accumulators of
+// the two block sums, [6] arrival counter, [7] "not representable" flag, [8..9] / [10..11] the two values as fp64.
+template <int GAMMA>
+__global__ void __launch_bounds__(256)
+view_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt_base, const int32_t* __restrict__ gt_index,
+                 int n_gt, size_t E, float eps, float bound, const float* __restrict__ upstream, float* __restrict__ dL_dx,
+                 float* __restrict__ work, float* __restrict__ l2_ema, const uint32_t* __restrict__ skip_flag) {
+  __shared__ double red[256];
+  int gi = (gt_index != nullptr) ? gt_index[0] : 0;
+  if (gi < 0 || gi >= n_gt) gi = 0;   // (a corrupt index must not read out of bounds; testpose_kernel does the same)
+  const float* gt = gt_base + (size_t)gi * E;
+  const float up = (upstream != nullptr) ? upstream[0] : 1.0f;
+  const float c_l1 = (float)((double)up / (double)E);
+  const float inv_span = 1.0f - 2.0f * bound;
+  const float ex = (float)(1.0 / 2.2), ex1 = (float)(1.0 / 2.2 - 1.0);
+  double l1 = 0.0, l2 = 0.0;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < E; e += (size_t)gridDim.x * 256) {
+    const float xv = x[e];
+    float y0 = xv, dy = 1.0f;
+    if (GAMMA) {
+      const float u = (xv - bound) / inv_span;
+      const float uc = fmaxf(u, eps);
+      y0 = powf(uc, ex);
+      // d/dx of clamp_min(u, eps) ^ ex: zero below eps, (ex * uc ^ (ex - 1)) / (1 - 2 bound) from eps on
+      dy = (u >= eps) ? (ex * powf(uc, ex1)) / inv_span : 0.0f;
+    }
+    const float y = fminf(1.0f, fmaxf(0.0f, y0));
+    const bool pass = y0 >= 0.0f && y0 <= 1.0f;   // torch.clamp passes the gradient inside and on the bounds
+    const float d = y - gt[e];
+    l1 += (double)fabsf(d);
+    l2 += (double)d * (double)d;
+    if (dL_dx != nullptr) dL_dx[e] = (pass && dy != 0.0f) ? (c_l1 * sgnf(d)) * dy : 0.0f;
+  }
+  if (work == nullptr) return;
+  const double a = block_sum_256(l1, red), c = block_sum_256(l2, red);
+  if (threadIdx.x != 0) return;
+  constexpr double FX = 16777216.0;   // 2^24
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(work + 2);
+  unsigned int* flag = reinterpret_cast<unsigned int*>(work + 7);
+  const bool fin = __builtin_isfinite(a) && __builtin_isfinite(c) && a < 5.0e11 && c < 5.0e11;
+  if (!fin) {
+    atomicOr(flag, 1u);
+  } else {
+    const unsigned long long ia = (unsigned long long)__double2ll_rn(a * FX);
+    const unsigned long long ic = (unsigned long long)__double2ll_rn(c * FX);
+    const unsigned long long oa = atomicAdd(&acc[0], ia), oc = atomicAdd(&acc[1], ic);
+    if (oa + ia < oa || oc + ic < oc) atomicOr(flag, 1u);
+  }
+  __threadfence();
+  const unsigned int ticket = atomicAdd(reinterpret_cast<unsigned int*>(work + 6), 1u);
+  if (ticket == gridDim.x - 1) {
+    __threadfence();
+    const unsigned long long t0 = atomicAdd(&acc[0], 0ull), t1 = atomicAdd(&acc[1], 0ull);
+    const bool bad = atomicOr(flag, 0u) != 0u;
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    const double v1 = bad ? nanv : ((double)t0 / FX) / (double)E;
+    const double v2 = bad ? nanv : ((double)t1 / FX) / (double)E;
+    work[0] = (float)v1;
+    work[1] = (float)v2;
+    reinterpret_cast<double*>(work + 8)[0] = v1;
+    reinterpret_cast<double*>(work + 8)[1] = v2;
+    // l2_error_ema = 0.6 l2_error_ema + 0.4 mse (test.py:178); a step whose forward overflowed its capacity does not count
+    if (l2_ema != nullptr && (skip_flag == nullptr || skip_flag[0] == 0u)) l2_ema[0] = l2_ema[0] * 0.6f + (float)v2 * 0.4f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------- PSNR + SSIM
+// One block per 16 x 16 output tile of one channel.  The (16 + 10)^2 halo of both images goes to LDS (zeros outside the
+// image: conv2d's zero padding), the 11-tap Gaussian runs along x for the five windowed quantities (a, b, a^2, b^2, a b),
+// then along y; arithmetic in fp64 (the variance terms are differences of nearly equal numbers; the kernel is far from
+// any fp64 limit: 110 multiply-adds per pixel and channel).  The block writes its SSIM-map sum and its squared-error sum
+// to partials[block][2]; metrics_reduce_kernel adds the blocks of every channel in index order.
+constexpr int MT = 16, MR = 5, MH = MT + 2 * MR;   // tile, window radius, tile + halo
+
+struct SsimWindow {
+  float w[2 * MR + 1];
+};
+
+__global__ void __launch_bounds__(256)
+metrics_tile_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W, SsimWindow win,
+                    double* __restrict__ partials) {
+  __shared__ double s_a[MH][MH + 1], s_b[MH][MH + 1];
+  __shared__ double s_h[5][MH][MT + 1];
+  __shared__ double red[256];
+  const int ch = blockIdx.z;
+  const int x0 = blockIdx.x * MT, y0 = blockIdx.y * MT;
+  const float* pa = a + (size_t)ch * H * W;
+  const float* pb = b + (size_t)ch * H * W;
+  double se = 0.0;
+  for (int i = threadIdx.x; i < MH * MH; i += 256) {
+    const int ly = i / MH, lx = i % MH;
+    const int gy = y0 + ly - MR, gx = x0 + lx - MR;
+    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
+    const double va = in ? (double)pa[(size_t)gy * W + gx] : 0.0;
+    const double vb = in ? (double)pb[(size_t)gy * W + gx] : 0.0;
+    s_a[ly][lx] = va;
+    s_b[ly][lx] = vb;
+    // the squared error of the tile's own pixels (PSNR)
+    if (in && ly >= MR && ly < MR + MT && lx >= MR && lx < MR + MT) se += (va - vb) * (va - vb);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < MH * MT; i += 256) {
+    const int ly = i / MT, lx = i % MT;
+    double ha = 0.0, hb = 0.0, haa = 0.0, hbb = 0.0, hab = 0.0;
+#pragma unroll
+    for (int t = 0; t < 2 * MR + 1; t++) {
+      const double w = (double)win.w[t];
+      const double va = s_a[ly][lx + t], vb = s_b[ly][lx + t];
+      ha += w * va;
+      hb += w * vb;
+      haa += w * (va * va);
+      hbb += w * (vb * vb);
+      hab += w * (va * vb);
+    }
+    s_h[0][ly][lx] = ha;
+    s_h[1][ly][lx] = hb;
+    s_h[2][ly][lx] = haa;
+    s_h[3][ly][lx] = hbb;
+    s_h[4][ly][lx] = hab;
+  }
+  __syncthreads();
+  const int ly = threadIdx.x / MT, lx = threadIdx.x % MT;
+  double ss = 0.0;
+  if (y0 + ly < H && x0 + lx < W) {
+    double mu1 = 0.0, mu2 = 0.0, e11 = 0.0, e22 = 0.0, e12 = 0.0;
+#pragma unroll
+    for (int t = 0; t < 2 * MR + 1; t++) {
+      const double w = (double)win.w[t];
+      mu1 += w * s_h[0][ly + t][lx];
+      mu2 += w * s_h[1][ly + t][lx];
+      e11 += w * s_h[2][ly + t][lx];
+      e22 += w * s_h[3][ly + t][lx];
+      e12 += w * s_h[4][ly + t][lx];
+    }
+    const double mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
+    const double sigma1_sq = e11 - mu1_sq, sigma2_sq = e22 - mu2_sq, sigma12 = e12 - mu1_mu2;
+    const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+    ss = ((2.0 * mu1_mu2 + C1) * (2.0 * sigma12 + C2)) / ((mu1_sq + mu2_sq + C1) * (sigma1_sq + sigma2_sq + C2));
+  }
+  const double tot_ss = block_sum_256(ss, red), tot_se = block_sum_256(se, red);
+  if (threadIdx.x == 0) {
+    const size_t blk = ((size_t)ch * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    partials[2 * blk] = tot_ss;
+    partials[2 * blk + 1] = tot_se;
+  }
+}
+
+// out[0] = mean over the channels of 20 log10(1 / sqrt(mse_c)), out[1] = mean of the SSIM map, out[2 + c] = the PSNR of
+// channel c
+__global__ void __launch_bounds__(256)
+metrics_reduce_kernel(const double* __restrict__ partials, int blocks_per_channel, int C, double HW,
+                      float* __restrict__ out) {
+  __shared__ double red[256];
+  double psnr = 0.0, ssim = 0.0;
+  for (int c = 0; c < C; c++) {
+    double ss = 0.0, se = 0.0;
+    for (int i = threadIdx.x; i < blocks_per_channel; i += 256) {
+      ss += partials[2 * ((size_t)c * blocks_per_channel + i)];
+      se += partials[2 * ((size_t)c * blocks_per_channel + i) + 1];
+    }
+    ss = block_sum_256(ss, red);
+    se = block_sum_256(se, red);
+    ssim += ss;
+    const double db = 20.0 * log10(1.0 / sqrt(se / HW));
+    psnr += db;
+    if (threadIdx.x == 0) out[2 + c] = (float)db;
+  }
+  if (threadIdx.x == 0) {
+    out[0] = (float)(psnr / (double)C);
+    out[1] = (float)(ssim / (HW * (double)C));
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dgs_view_loss_grad(const float* x, const float* gt, const int32_t* gt_index_dev, int32_t n_gt, int32_t C, int32_t HW,
+                       int32_t tone_mapping, float eps, float bound, const float* upstream, float* dL_dx, float* work,
+                       float* l2_ema, const uint32_t* skip_flag, dgs_stream_t stream) {
+  if (x == nullptr || gt == nullptr || n_gt < 1 || C < 1 || HW < 1 || (dL_dx == nullptr && work == nullptr))
+    return dgs_fail_arg("view_loss_grad: null image, empty image or no output requested");
+  if (tone_mapping != DGS_TONE_IDENTITY && tone_mapping != DGS_TONE_GAMMA)
+    return dgs_fail_arg("view_loss_grad: tone_mapping must be DGS_TONE_IDENTITY or DGS_TONE_GAMMA");
+  if (tone_mapping == DGS_TONE_GAMMA && !(bound < 0.5f)) return dgs_fail_arg("view_loss_grad: bound must be below 0.5");
+  if (l2_ema != nullptr && work == nullptr) return dgs_fail_arg("view_loss_grad: l2_ema needs the work area");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t E = (size_t)C * (size_t)HW;
+  if (work != nullptr) {
+    hipError_t e = dgs_launch_clear_words(reinterpret_cast<uint32_t*>(work), 12, s);
+    if (e != hipSuccess) return dgs_fail_hip(e, "view_loss_grad (clear)");
+  }
+  const size_t want = (E + 255) / 256;
+  const dim3 grid((uint32_t)(want < 1024 ? want : 1024));   // a function of E only: the totals are reproducible
+  if (tone_mapping == DGS_TONE_GAMMA)
+    hipLaunchKernelGGL(view_loss_kernel<1>, grid, dim3(256), 0, s, x, gt, gt_index_dev, (int)n_gt, E, eps, bound, upstream, dL_dx, work,
+                       l2_ema, skip_flag);
+  else
+    hipLaunchKernelGGL(view_loss_kernel<0>, grid, dim3(256), 0, s, x, gt, gt_index_dev, (int)n_gt, E, eps, bound, upstream, dL_dx, work,
+                       l2_ema, skip_flag);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "view_loss_grad");
+}
+
+size_t dgs_image_metrics_tmp_bytes(int32_t W, int32_t H) {
+  if (W < 1 || H < 1) return 0;
+  return (size_t)3 * ((W + MT - 1) / MT) * ((H + MT - 1) / MT) * 2 * sizeof(double);
+}
+
+int dgs_image_metrics(const float* a, const float* b, int32_t W, int32_t H, void* tmp, float* out, dgs_stream_t stream) {
+  if (a == nullptr || b == nullptr || tmp == nullptr || out == nullptr || W < 1 || H < 1)
+    return dgs_fail_arg("image_metrics: null pointer or empty image");
+  const int gx = (W + MT - 1) / MT, gy = (H + MT - 1) / MT;
+  if (gy > 65535) return dgs_fail_arg("image_metrics: image too tall");
+  // the window of utils/loss_utils.py:23-25 with its roundings: fp32 samples of exp(-(x - 5)^2 / (2 sigma^2)), their fp32
+  // sum, an fp32 division
+  SsimWindow win;
+  float sum = 0.0f;
+  for (int i = 0; i < 2 * MR + 1; i++) {
+    win.w[i] = (float)exp(-(double)((i - MR) * (i - MR)) / (2.0 * 1.5 * 1.5));
+    sum += win.w[i];
+  }
+  for (int i = 0; i < 2 * MR + 1; i++) win.w[i] = win.w[i] / sum;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  double* partials = reinterpret_cast<double*>(tmp);
+  hipLaunchKernelGGL(metrics_tile_kernel, dim3(gx, gy, 3), dim3(256), 0, s, a, b, (int)H, (int)W, win, partials);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dgs_fail_hip(e, "image_metrics");
+  hipLaunchKernelGGL(metrics_reduce_kernel, dim3(1), dim3(256), 0, s, partials, gx * gy, 3, (double)W * (double)H, out);
+  e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "image_metrics");
+}
+
+}  // extern "C"

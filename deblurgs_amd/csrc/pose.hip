@@ -313,6 +313,78 @@ __global__ void alignment_bwd_kernel(int f, int n_sub, const float* __restrict__
   dL_draw[i - 1] = dL_dnu[r] * pass * (sg * (1.0f - sg));
 }
 
+// ---- the pose chain of the test-view fit (test.py:72-91, OptimPoseModel.forward) for ONE view, the view's index read
+// from device memory: quat = rot[idx] + 1e-8 (fp32), unit quaternion (x, y, z, w), rotation matrix (quat_rot above),
+//   world_view[:3,:3] = R, world_view[3,:3] = trans[idx], full_proj = world_view @ proj,
+//   camera_center = inverse(world_view)[3,:3] = -trans R^T
+// MODE 0: the three camera tensors (one thread).  MODE 1: dL/dquat and dL/dtrans from dL/d{world_view, full_proj}, written
+// into row idx of the [n,4] / [n,3] gradient buffers whose other rows are zeroed here (torch's dense gradient of an
+// indexed parameter): thread t < 4 n owns rot-gradient element t (row idx: quaternion component t & 3, differentiated with
+// one dual direction), the next 3 n threads own the translation gradient.  The camera centre carries no gradient: the
+// rasteriser returns none for campos.
+template <int MODE>
+__global__ void testpose_kernel(const float* __restrict__ rot, const float* __restrict__ trans,
+                                const int32_t* __restrict__ idx_dev, int idx, int n, const float* __restrict__ proj,
+                                float* __restrict__ view, float* __restrict__ full, float* __restrict__ campos,
+                                const float* __restrict__ dL_dview, const float* __restrict__ dL_dfull,
+                                float* __restrict__ dL_drot, float* __restrict__ dL_dtrans) {
+  if (idx_dev != nullptr) idx = idx_dev[0];
+  if (idx < 0 || idx >= n) idx = 0;   // (a corrupt index must not read out of bounds)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (MODE == 0) {
+    if (t != 0) return;
+    D6 q[4], R[9];
+    for (int i = 0; i < 4; i++) q[i] = cst((double)(rot[4 * idx + i] + 1e-8f));
+    quat_rot(q, R);
+    float wv[16];
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) wv[4 * r + c] = (float)R[3 * r + c].v;
+      wv[4 * r + 3] = 0.0f;
+    }
+    for (int c = 0; c < 3; c++) wv[12 + c] = trans[3 * idx + c];
+    wv[15] = 1.0f;
+    for (int i = 0; i < 16; i++) view[i] = wv[i];
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) {
+        float acc = 0.0f;
+        for (int j = 0; j < 4; j++) acc += wv[4 * r + j] * proj[4 * j + c];
+        full[4 * r + c] = acc;
+      }
+    for (int d = 0; d < 3; d++)
+      campos[d] = (float)(-((double)wv[12] * R[3 * d].v + (double)wv[13] * R[3 * d + 1].v + (double)wv[14] * R[3 * d + 2].v));
+  } else {
+    if (t >= 7 * n) return;
+    const bool is_rot = t < 4 * n;
+    const int row = is_rot ? (t >> 2) : (t - 4 * n) / 3;
+    const int comp = is_rot ? (t & 3) : (t - 4 * n) % 3;
+    float g = 0.0f;
+    if (row == idx) {
+      // G = dL/dworld_view = dL_dview + dL_dfull @ P^T (the rows this thread needs)
+      if (is_rot) {
+        D6 q[4], R[9];
+        for (int i = 0; i < 4; i++) q[i] = var((double)(rot[4 * idx + i] + 1e-8f), i == comp);
+        quat_rot(q, R);
+        double acc = 0.0;
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) {
+            double G = (double)dL_dview[4 * r + c];
+            for (int j = 0; j < 4; j++) G += (double)dL_dfull[4 * r + j] * (double)proj[4 * c + j];
+            acc += G * R[3 * r + c].d[0];
+          }
+        g = (float)acc;
+      } else {
+        double G = (double)dL_dview[12 + comp];
+        for (int j = 0; j < 4; j++) G += (double)dL_dfull[12 + j] * (double)proj[4 * comp + j];
+        g = (float)G;
+      }
+    }
+    if (is_rot)
+      dL_drot[t] = g;
+    else
+      dL_dtrans[t - 4 * n] = g;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -371,6 +443,27 @@ int dgs_pose_backward(const float* ctrl_trans, const float* ctrl_rot, const floa
                        nullptr, nullptr, nullptr, dL_dview, dL_dfull, dse3, dL_dnu, coeff);
   hipLaunchKernelGGL(pose_ctrl_grad_kernel, dim3(1), dim3(256), 0, s, C, K, quaternion ? 7 : 6, coeff, dse3,
                      dL_dctrl_trans, dL_dctrl_rot);
+  return hipGetLastError() == hipSuccess ? DGS_OK : DGS_E_HIP;
+}
+
+int dgs_testpose_forward(const float* rot, const float* trans, const int32_t* idx_dev, int32_t idx, int32_t n,
+                         const float* proj, float* view, float* full, float* campos, dgs_stream_t stream) {
+  if (rot == nullptr || trans == nullptr || proj == nullptr || view == nullptr || full == nullptr || campos == nullptr ||
+      n < 1 || (idx_dev == nullptr && (idx < 0 || idx >= n)))
+    return DGS_E_ARG;
+  hipLaunchKernelGGL(testpose_kernel<0>, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), rot, trans, idx_dev,
+                     idx, n, proj, view, full, campos, nullptr, nullptr, nullptr, nullptr);
+  return hipGetLastError() == hipSuccess ? DGS_OK : DGS_E_HIP;
+}
+
+int dgs_testpose_backward(const float* rot, const float* trans, const int32_t* idx_dev, int32_t idx, int32_t n,
+                          const float* proj, const float* dL_dview, const float* dL_dfull, float* dL_drot,
+                          float* dL_dtrans, dgs_stream_t stream) {
+  if (rot == nullptr || trans == nullptr || proj == nullptr || dL_dview == nullptr || dL_dfull == nullptr ||
+      dL_drot == nullptr || dL_dtrans == nullptr || n < 1 || n > (1 << 24) || (idx_dev == nullptr && (idx < 0 || idx >= n)))
+    return DGS_E_ARG;
+  hipLaunchKernelGGL(testpose_kernel<1>, dim3((7 * n + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), rot,
+                     trans, idx_dev, idx, n, proj, nullptr, nullptr, nullptr, dL_dview, dL_dfull, dL_drot, dL_dtrans);
   return hipGetLastError() == hipSuccess ? DGS_OK : DGS_E_HIP;
 }
 

@@ -1,0 +1,419 @@
+"""The reference's evaluation protocol (test.py): the learned trajectories make a dataset's test poses invalid, so every
+number the reference reports comes from
+
+    optimize_test_pose   test.py:131-186   an iNeRF-style fit of the test cameras to the trained cloud: per step one
+                                           render, a tone-mapped and clamped L1 against the test image, a backward into the
+                                           CAMERA only, one Adam step on a quaternion and a translation
+    evaluate             test.py:93-129    PSNR / SSIM (/ LPIPS) of the renders at the fitted cameras
+
+`TestPoseModel` is OptimPoseModel (test.py:39-91).  `FusedPoseFit` is one step of the fit enqueued straight through the C
+ABI and replayed as ONE captured hipGraph -- no autograd, no host read:
+
+    quaternion + translation of the drawn view -> camera     dgs_testpose_forward   (view index from device memory)
+    K = 1 rasterisation of the cloud's raw parameters        dgs_forward            (capacity sized ahead)
+    clamp(tone_map(render), 0, 1), L1, MSE, dL/drender       dgs_view_loss_grad
+    dL/d{world_view, full_proj}, nothing else                dgs_backward_pose_only
+    -> dL/dquaternion, dL/dtranslation (dense [n,4], [n,3])  dgs_testpose_backward
+    Adam on the two tensors                                  dgs_adam_step_dev      (step sizes from device memory)
+
+The graph is a linear chain (the pose-only backward never forks).  What changes between steps -- the view index and Adam's
+bias-corrected step sizes, which carry the StepLR stage -- is read from an 8-word device block that a one-launch copy
+refreshes from the run's schedule before every replay, so one capture serves every view and every learning-rate stage.
+
+Semantics are the reference's: Adam (rates 5e-5 / 5e-4, eps 1e-15) runs over the WHOLE [n,4] and [n,3] tensors every step
+(rows with zero gradient still move by their momentum, as torch's dense Adam moves them), StepLR(num_iter // 20, 0.9)
+advances once per epoch, an epoch visits every view once in shuffled order.
+
+LPIPS is not computed (its network weights are not part of this package); `evaluate` returns (psnr, ssim).
+`initialize_test_pose` (COLMAP registration of unposed test images) and the dataset readers are out of scope.
+"""
+import ctypes
+import math
+import random
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib, gaussian_renderer, losses, metrics, pose, raster_call
+from . import diff_gaussian_rasterization as dgr
+from .raster_call import _ptr, _stream
+
+ROT_LR, TRANS_LR, ADAM_EPS = 5e-5, 5e-4, 1e-15      # test.py:146-149
+LR_STAGES, LR_GAMMA = 20, 0.9                        # test.py:151
+
+
+class TestCamera:
+    """The attributes of the reference's Camera that the evaluation reads (scene/cameras.py): R [3,3] (stored as the
+    camera-to-world rotation, as the reference's loaders store it) and T [3] of the world-to-view transform, the
+    intrinsics, and the test image."""
+    __test__ = False      # (not a pytest class)
+
+    def __init__(self, R, T, FoVx, FoVy, image_width, image_height, original_image=None, znear=0.01, zfar=100.0):
+        self.R, self.T = np.asarray(R, dtype=np.float64), np.asarray(T, dtype=np.float64)
+        self.FoVx, self.FoVy = float(FoVx), float(FoVy)
+        self.image_width, self.image_height = int(image_width), int(image_height)
+        self.znear, self.zfar = float(znear), float(zfar)
+        self.original_image = original_image
+
+
+def _as_tensor(a):
+    return a.detach().double().cpu() if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, dtype=np.float64))
+
+
+class TestPoseModel(nn.Module):
+    """OptimPoseModel (test.py:39-91): `_rot` [n,4] unit quaternions in (x, y, z, w) order from the cameras' rotations
+    (pose.rotmat_to_unitquat: the algorithm roma documents for rotmat_to_unitquat, pinned against scipy -- unpinned
+    against roma itself, which is not available here), `_trans` [n,3] their translations.  forward(idx) is the torch
+    expression of the pose chain (differentiable; what the autograd path of the fit runs); FusedPoseFit evaluates the
+    same chain with dgs_testpose_forward / _backward."""
+    __test__ = False
+
+    def __init__(self, cams, device=None):
+        super().__init__()
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.cams = list(cams)
+        rots = torch.stack([_as_tensor(c.R) for c in self.cams])
+        transes = torch.stack([_as_tensor(c.T) for c in self.cams])
+        self._rot = nn.Parameter(pose.rotmat_to_unitquat(rots).float().to(device).contiguous())
+        self._trans = nn.Parameter(transes.float().to(device).contiguous())
+        self._proj = {}
+
+    def __len__(self):
+        return len(self.cams)
+
+    def projection_matrix(self, idx):
+        """The transposed projection matrix of view idx on the model's device (test.py:87), cached per intrinsics."""
+        c = self.cams[idx]
+        key = (c.znear, c.zfar, c.FoVx, c.FoVy)
+        if key not in self._proj:
+            self._proj[key] = pose.get_projection_matrix(znear=c.znear, zfar=c.zfar, fovX=c.FoVx, fovY=c.FoVy) \
+                .transpose(0, 1).contiguous().to(self._rot.device)
+        return self._proj[key]
+
+    def forward(self, idx):
+        """A camera carrying the four tensors render() reads (world_view_transform, full_proj_transform, camera_center,
+        and projection_matrix) plus the intrinsics and the test image of view idx."""
+        c = self.cams[idx]
+        quat = self._rot[idx] + 1e-8
+        unit = quat / quat.norm()
+        R = pose.unitquat_to_rotmat(unit[None])[0]
+        trans = self._trans[idx]
+        # world_view[:3,:3] = (R^T)^T, world_view[3,:3] = trans: test.py:82-85 after its final transpose
+        top = torch.cat([R, R.new_zeros(3, 1)], dim=1)
+        bottom = torch.cat([trans, trans.new_ones(1)])[None]
+        wv = torch.cat([top, bottom], dim=0)
+        proj = self.projection_matrix(idx).to(wv.dtype)
+        cam = pose.MiniCam(c.image_width, c.image_height, c.FoVy, c.FoVx, c.znear, c.zfar, wv, wv @ proj,
+                           camera_center=-(trans @ R.transpose(0, 1)))       # = inverse(world_view)[3,:3]
+        cam.projection_matrix = proj
+        cam.original_image = getattr(c, "original_image", None)
+        return cam
+
+
+def view_loss(image, gt, tone_mapping):
+    """The fit's loss in torch (test.py:171-172): L1 of clamp(tone_map(image), 0, 1) against gt.  Returns (l1, mse)."""
+    y = tone_mapping(image).clamp(0.0, 1.0)
+    return losses.l1_loss(y, gt), ((gt - y) ** 2).mean()
+
+
+def _tone_args(tone_mapping):
+    if tone_mapping is None or isinstance(tone_mapping, str):
+        tone_mapping = losses.ToneMapping(tone_mapping or "identity")
+    kind = tone_mapping.tone_mapping_type
+    if kind in ("identity", "reverse_identity"):
+        return tone_mapping, _lib.TONE_IDENTITY, 0.0, 0.0
+    if kind == "gamma":
+        return tone_mapping, _lib.TONE_GAMMA, float(tone_mapping.eps), float(tone_mapping.bound)
+    raise NotImplementedError(f"FusedPoseFit implements the identity and gamma tone mappings (got {kind!r})")
+
+
+def epoch_orders(n, epochs, seed=None, order=None):
+    """The view order of every epoch.  order None: a shuffle per epoch, drawn and consumed as test.py:159-165 does
+    (random.shuffle, then pop() from the END) from a generator seeded with `seed` (None: the global `random` state);
+    a list of n indices: that order every epoch; a list of lists: one per epoch."""
+    if order is not None:
+        order = [list(o) for o in order] if (len(order) and isinstance(order[0], (list, tuple))) else [list(order)] * epochs
+        if len(order) != epochs or any(sorted(o) != list(range(n)) for o in order):
+            raise ValueError("order must be a permutation of the views, or one permutation per epoch")
+        return order
+    rng = random if seed is None else random.Random(seed)
+    out = []
+    for _ in range(epochs):
+        idx = list(range(n))
+        rng.shuffle(idx)
+        out.append(idx[::-1])
+    return out
+
+
+def step_lrs(epochs, num_iter_per_view):
+    """(rot lr, trans lr) of every epoch under StepLR(step_size = num_iter_per_view // 20, gamma = 0.9), advanced once per
+    epoch; the products are formed one stage at a time, as the scheduler forms them."""
+    step_size = max(int(num_iter_per_view) // LR_STAGES, 1)
+    lr = [ROT_LR, TRANS_LR]
+    out = []
+    for e in range(epochs):
+        if e > 0 and e % step_size == 0:
+            lr = [x * LR_GAMMA for x in lr]
+        out.append(tuple(lr))
+    return out
+
+
+class FusedPoseFit:
+    HYPER_WORDS = 8      # [0] view index (int32), [1:5] Adam's (-(lr / (1 - beta1^t)), sqrt(1 - beta2^t)) for rot, trans
+
+    def __init__(self, cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, model=None, tile_cull=None,
+                 capacity=None):
+        """cloud: a GaussianCloud (fused_activations); cams: the test cameras (all of one image size and field of view);
+        gt_images: [n,3,H,W] or a list of [3,H,W]; bg: [3]; tone_mapping: losses.ToneMapping("identity" | "gamma") or its
+        name.  capacity: duplicates the lists are sized for (None: 1.5 x the largest count over the views at their
+        start poses + 16384, learnt with one exact forward per view here, outside the loop)."""
+        if not getattr(cloud, "fused_activations", False):
+            raise NotImplementedError("FusedPoseFit needs a cloud with fused_activations")
+        self.cloud = cloud
+        dev = cloud._xyz.device
+        if dev.type != "cuda":
+            raise RuntimeError("FusedPoseFit needs a cloud on a HIP device (no CPU fallback)")
+        self.model = model if model is not None else TestPoseModel(cams, device=dev)
+        m = self.model
+        self.n = n = len(m)
+        c0 = m.cams[0]
+        for c in m.cams:
+            if (c.image_width, c.image_height, c.FoVx, c.FoVy, c.znear, c.zfar) != \
+                    (c0.image_width, c0.image_height, c0.FoVx, c0.FoVy, c0.znear, c0.zfar):
+                raise NotImplementedError("FusedPoseFit captures one step for all views: they must share image size and "
+                                          "intrinsics (fit views of different sizes with one FusedPoseFit each)")
+        self.H, self.W = H, W = int(c0.image_height), int(c0.image_width)
+        self.num_iter_per_view = int(num_iter_per_view)
+        self.tone_mapping, self._tone, self._eps, self._bound = _tone_args(tone_mapping)
+        f32 = dict(dtype=torch.float32, device=dev)
+        gt = torch.stack(list(gt_images)) if not torch.is_tensor(gt_images) else gt_images
+        self.gt = gt.to(**f32).contiguous()
+        if tuple(self.gt.shape) != (n, 3, H, W):
+            raise ValueError(f"gt_images must be [{n},3,{H},{W}]")
+        self.bg = bg.to(**f32).contiguous()
+        self.proj = m.projection_matrix(0).to(**f32).contiguous()
+        self.cull = dgr.TILE_CULL if tile_cull is None else bool(tile_cull)
+        self.steps = 0                # Adam steps enqueued so far (the bias-correction exponent)
+        self._sched = None
+        self._graph = None
+        P = cloud._xyz.shape[0]
+        L = _lib.lib()
+        # ---- every buffer of the step, allocated once: the captured graph bakes their addresses in
+        self.hyper = torch.zeros(self.HYPER_WORDS, **f32)
+        self.view, self.full, self.campos = torch.empty((1, 4, 4), **f32), torch.empty((1, 4, 4), **f32), torch.empty((1, 3), **f32)
+        self.color = torch.empty((1, 3, H, W), **f32)
+        self.dcolor = torch.empty((1, 3, H, W), **f32)
+        self.radii = torch.empty((1, P), dtype=torch.int32, device=dev)
+        self.work = torch.zeros(12, **f32)           # dgs_view_loss_grad's work area: [0] l1, [1] mse
+        self.l2_ema = torch.zeros(1, **f32)          # the reference's l2_error_ema, on the device
+        self.drops = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.g_view, self.g_proj = torch.empty((1, 4, 4), **f32), torch.empty((1, 4, 4), **f32)
+        self.g_rot, self.g_trans = torch.empty((n, 4), **f32), torch.empty((n, 3), **f32)
+        self.exp_avg = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
+        self.exp_avg_sq = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
+        self._host = torch.zeros(8, dtype=torch.int32).pin_memory()
+        self._geom = torch.empty(L.dgs_geom_state_bytes(P, 1), dtype=torch.uint8, device=dev)
+        self._image = torch.empty(L.dgs_image_state_bytes(W, H, 1), dtype=torch.uint8, device=dev)
+        self.capacity = int(capacity) if capacity is not None else self._learn_capacity()
+        self._binning = torch.empty(L.dgs_binning_state_bytes(self.capacity, W, H, 1), dtype=torch.uint8, device=dev)
+        self._scratch = torch.empty(L.dgs_backward_scratch_bytes(self.capacity, P, 1), dtype=torch.uint8, device=dev)
+        self._skip_ptr = self._geom.data_ptr() + raster_call.skip_word_offset(P, W, H, 1)
+        self._prob, self._out, self._io, self._groups = self._structs()
+
+    # ------------------------------------------------------------------------------------------------ plumbing
+    def _settings(self):
+        cloud, c0 = self.cloud, self.model.cams[0]
+        return dgr.GaussianRasterizationSettings(
+            image_height=self.H, image_width=self.W, tanfovx=math.tan(c0.FoVx * 0.5), tanfovy=math.tan(c0.FoVy * 0.5),
+            bg=self.bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
+            sh_degree=cloud.active_sh_degree, campos=self.campos, prefiltered=False, debug=False)
+
+    def _problem(self, binning=None):
+        cloud = self.cloud
+        rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
+        raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
+        return raster_call.problem(1, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
+                                   None, self.view, self.full, self.campos, self._settings(), self.bg, self.cull, 0, raw=raw,
+                                   geom=self._geom, image=self._image, binning=binning)
+
+    def _pose_forward(self, idx_dev, idx, stream):
+        m = self.model
+        _lib.check(_lib.lib().dgs_testpose_forward(_ptr(m._rot), _ptr(m._trans), idx_dev, int(idx), self.n, _ptr(self.proj),
+                                                   _ptr(self.view), _ptr(self.full), _ptr(self.campos), stream),
+                   "dgs_testpose_forward")
+
+    @torch.no_grad()
+    def _learn_capacity(self):
+        """One exact (two-phase) forward per view at its start pose: the largest duplicate count, with half as much again
+        for the poses the fit moves through."""
+        dev = self.cloud._xyz.device
+        need = 0
+        for i in range(self.n):
+            self._pose_forward(None, i, _stream(dev))
+            prob = self._problem()
+            out = raster_call.forward_out(self.color, None, self.radii, self._host)
+            R, _ = raster_call.forward(dev, prob, out, self._host, None)
+            need = max(need, int(R))
+        cap = need + need // 2 + 16384
+        q = 1 << max(cap.bit_length() - 5, 10)
+        return -(-cap // q) * q
+
+    def _structs(self):
+        m = self.model
+        prob = self._problem(self._binning)
+        out = raster_call.forward_out(self.color, None, self.radii, self._host, drop_counter=self.drops)
+        io = _lib.DgsBackwardIO()
+        io.num_rendered = self.capacity
+        io.radii, io.dL_dout_color = _ptr(self.radii), _ptr(self.dcolor)
+        io.scratch, io.scratch_bytes = _ptr(self._scratch), self._scratch.numel()
+        io.dL_dviewmatrix, io.dL_dprojmatrix = _ptr(self.g_view), _ptr(self.g_proj)
+        groups = (_lib.DgsAdamGroup * 2)(
+            _lib.DgsAdamGroup(m._rot.data_ptr(), self.g_rot.data_ptr(), self.exp_avg[0].data_ptr(),
+                              self.exp_avg_sq[0].data_ptr(), m._rot.numel(), ROT_LR, 1),
+            _lib.DgsAdamGroup(m._trans.data_ptr(), self.g_trans.data_ptr(), self.exp_avg[1].data_ptr(),
+                              self.exp_avg_sq[1].data_ptr(), m._trans.numel(), TRANS_LR, 1))
+        return prob, out, io, groups
+
+    @torch.no_grad()
+    def _enqueue(self, apply=True):
+        """The six launches of one step on the current stream, everything read from the device block `hyper`."""
+        L = _lib.lib()
+        m = self.model
+        dev = self.cloud._xyz.device
+        stream = _stream(dev)
+        idx_dev = ctypes.c_void_p(self.hyper.data_ptr())
+        skip = ctypes.c_void_p(self._skip_ptr)
+        self._pose_forward(idx_dev, 0, stream)
+        _lib.check(L.dgs_forward(ctypes.byref(self._prob), ctypes.byref(self._out), self.capacity, stream), "dgs_forward")
+        _lib.check(L.dgs_view_loss_grad(_ptr(self.color), _ptr(self.gt), idx_dev, self.n, 3, self.H * self.W, self._tone, self._eps,
+                                        self._bound, None, _ptr(self.dcolor), _ptr(self.work),
+                                        _ptr(self.l2_ema) if apply else None, skip, stream), "dgs_view_loss_grad")
+        _lib.check(L.dgs_backward_pose_only(ctypes.byref(self._prob), ctypes.byref(self._io), stream),
+                   "dgs_backward_pose_only")
+        _lib.check(L.dgs_testpose_backward(_ptr(m._rot), _ptr(m._trans), idx_dev, 0, self.n, _ptr(self.proj),
+                                           _ptr(self.g_view), _ptr(self.g_proj), _ptr(self.g_rot), _ptr(self.g_trans),
+                                           stream), "dgs_testpose_backward")
+        if apply:
+            _lib.check(L.dgs_adam_step_dev(self._groups, 2, 0.9, 0.999, ADAM_EPS, 0.0, skip,
+                                           ctypes.c_void_p(self.hyper.data_ptr() + 4), stream), "dgs_adam_step_dev")
+
+    @torch.no_grad()
+    def gradients(self, idx):
+        """One step WITHOUT its update, enqueued eagerly: the dense (dL/drot [n,4], dL/dtrans [n,3]) of view idx and the
+        loss values (l1, mse) as device tensors.  (Also what loads every kernel of the step before the capture.)"""
+        self.hyper[:1].copy_(torch.tensor([int(idx)], dtype=torch.int32).view(torch.float32))
+        self._enqueue(apply=False)
+        return self.g_rot.clone(), self.g_trans.clone(), self.work[:2].clone()
+
+    def _capture(self):
+        dev = self.cloud._xyz.device
+        self.gradients(0)                     # every kernel of the step has run once: nothing is loaded inside the capture
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                self._enqueue()
+        except RuntimeError as ex:
+            raise RuntimeError(f"the pose-fit step could not be captured into a hipGraph: {ex}") from ex
+        self._graph = graph
+
+    # ------------------------------------------------------------------------------------------------- the fit
+    def schedule(self, orders, first_epoch=0):
+        """Uploads the device schedule of a run -- one 8-word row per step: the view index and Adam's scalars for the
+        step's count and its epoch's learning rates -- and returns the number of steps.  orders: one view order per
+        epoch (epoch_orders); first_epoch: the StepLR epoch the first of them is."""
+        L = _lib.lib()
+        lrs = step_lrs(first_epoch + len(orders), self.num_iter_per_view)[first_epoch:]
+        rows = np.zeros((sum(len(o) for o in orders), self.HYPER_WORDS), dtype=np.float32)
+        t, i = self.steps, 0
+        tmp = (ctypes.c_float * 4)()
+        for order, (lr_rot, lr_trans) in zip(orders, lrs):
+            for idx in order:
+                t += 1
+                self._groups[0].lr, self._groups[0].step = lr_rot, t
+                self._groups[1].lr, self._groups[1].step = lr_trans, t
+                _lib.check(L.dgs_adam_scalars(self._groups, 2, 0.9, 0.999, tmp), "dgs_adam_scalars")
+                rows[i, :1].view(np.int32)[0] = int(idx)
+                rows[i, 1:5] = np.frombuffer(tmp, dtype=np.float32)
+                i += 1
+        self._sched = torch.from_numpy(rows).to(self.hyper.device)
+        self._sched_pos = 0
+        if self._graph is None:
+            self._capture()
+        return rows.shape[0]
+
+    def run(self, n_steps=None):
+        """Enqueues the next n_steps (default: all remaining) steps of the uploaded schedule: per step one small copy
+        launch (the step's row into the device block) and one graph launch.  No host synchronisation."""
+        L = _lib.lib()
+        dev = self.cloud._xyz.device
+        stream = _stream(dev)
+        left = self._sched.shape[0] - self._sched_pos
+        n_steps = left if n_steps is None else min(int(n_steps), left)
+        hyper = ctypes.c_void_p(self.hyper.data_ptr())
+        base, words = self._sched.data_ptr(), self.HYPER_WORDS
+        for i in range(self._sched_pos, self._sched_pos + n_steps):
+            _lib.check(L.dgs_copy_words(hyper, ctypes.c_void_p(base + 4 * words * i), words, stream), "dgs_copy_words")
+            self._graph.replay()
+        self._sched_pos += n_steps
+        self.steps += n_steps
+        return n_steps
+
+    def dropped(self):
+        """Steps whose duplicate count exceeded the capacity (a host read): their update was skipped on the device."""
+        return int(self.drops.item())
+
+    def psnr_ema(self):
+        """20 log10(1 / sqrt(l2_error_ema)) as the reference logs it (test.py:183); a host read."""
+        v = float(self.l2_ema.item())
+        return 20.0 * math.log10(1.0 / math.sqrt(v)) if v > 0.0 else float("inf")
+
+    def cameras(self):
+        with torch.no_grad():
+            return [self.model(i) for i in range(self.n)]
+
+
+def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, order=None, seed=None,
+                       log_every=0):
+    """test.py:131-186 on the fused step: fits the test cameras to the cloud and returns the fitted cameras
+    ([TestPoseModel(i) for i in range(n)]).  order: see epoch_orders (None: a seeded or global shuffle per epoch).
+    log_every > 0 prints the reference's progress line every that many epochs (one host read each)."""
+    fit = FusedPoseFit(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=num_iter_per_view)
+    epochs = int(num_iter_per_view)
+    orders = epoch_orders(fit.n, epochs, seed=seed, order=order)
+    chunk = int(log_every) if log_every and log_every > 0 else epochs
+    for e0 in range(0, epochs, max(chunk, 1)):
+        fit.schedule(orders[e0:e0 + chunk], first_epoch=e0)
+        fit.run()
+        if log_every and log_every > 0:
+            print(f"Optimizing...PSNR ={fit.psnr_ema():6.2f} epoch {min(e0 + chunk, epochs)}/{epochs}", flush=True)
+    torch.cuda.synchronize(cloud._xyz.device)
+    drops = fit.dropped()
+    if drops:
+        raise RuntimeError(f"{drops} of {fit.steps} pose-fit steps exceeded the duplicate capacity ({fit.capacity}) and "
+                           "were skipped; fit again with FusedPoseFit(capacity=...) sized for the poses it moves through")
+    return fit.cameras()
+
+
+@torch.no_grad()
+def evaluate(cams, cloud, bg, gt_images, tone_mapping):
+    """test.py:93-129 without LPIPS: (mean PSNR, mean SSIM) over the cameras.  The render of every camera goes through the
+    forward_only inference path (gaussian_renderer.render under no_grad), is tone-mapped and NOT clamped, and both metrics
+    come from one fused kernel per view (metrics.psnr / metrics.ssim)."""
+    if tone_mapping is None or isinstance(tone_mapping, str):
+        tone_mapping = losses.ToneMapping(tone_mapping or "identity")
+    psnr_test, ssim_test = 0.0, 0.0
+    n = len(cams)
+    for cam, gt in zip(cams, gt_images):
+        image = tone_mapping(gaussian_renderer.render(cam, cloud, bg)["render"]).contiguous()
+        gt = gt.to(image)
+        if image.device.type == "cuda":       # one launch for both: the values metrics.psnr / metrics.ssim return
+            both = metrics.psnr_ssim(image, gt.contiguous())
+            psnr_test += both[2:5].reshape(3, 1).mean().item()
+            ssim_test += both[1].mean().item()
+        else:
+            psnr_test += metrics.psnr(image, gt).mean().item()
+            ssim_test += metrics.ssim(image, gt).mean().item()
+    return psnr_test / n, ssim_test / n

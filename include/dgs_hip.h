@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DGS_ABI_VERSION 14
+#define DGS_ABI_VERSION 15
 #define DGS_MAX_K 128 /* subframes per fused call */
 
 #define DGS_OK 0
@@ -316,6 +316,22 @@ int dgs_backward_pose(const DgsProblem* p, const DgsBackwardIO* io, dgs_stream_t
  * this context (1 = one launch: no context, small view, K < 6, no tile culling, or bwd_overlap = 0).  For callers that
  * choose between replaying a captured step (always one launch) and enqueueing it eagerly: deblurgs_amd/fused_step.py does. */
 int32_t dgs_backward_parts(const DgsContext* ctx, int32_t K, uint64_t num_rendered, int32_t tile_cull);
+/* ABI 15.  The backward of a caller that optimises the CAMERAS only -- the test-view pose fit of the reference's evaluation
+ * (test.py:131-186: one render, a loss, a backward into the camera, one Adam step on a quaternion and a translation,
+ * tens of thousands of times per evaluation).  Reads what dgs_backward reads -- the state blobs, num_rendered, radii,
+ * dL_dout_color, optional dL_dout_depth, scratch (>= dgs_backward_scratch_bytes) -- and writes ONLY dL_dviewmatrix and
+ * dL_dprojmatrix [K,4,4]: the compositing backward without its colour sums, the per-pair totals of the columns that are
+ * left, then a per-Gaussian kernel that keeps the pose terms alone (no SH backward, no covariance -> scale / rotation
+ * chain, no per-Gaussian store).  The two matrices agree with dgs_backward's to fp32 rounding -- the same expressions
+ * compiled into two kernels contract different multiplies into FMAs: 3e-6 .. 9e-6 of the largest entry measured, held to
+ * 1e-4 by the tests -- NOT bit for bit; they are bit-reproducible from call to call.  The scratch holds this call's own
+ * row layout afterwards (eight columns per row), not dgs_backward's.  Every other gradient pointer and every stats_* field of `io` may be NULL and is never
+ * dereferenced.  Any K in 1..DGS_MAX_K, both tile_cull values, raw_params 0 / 1 / 3, colors_precomp, cov3D_precomp;
+ * DGS_E_ARG for a forward_only problem and for a NULL pose output.  On a state whose lists were truncated (status word
+ * [5], capacity mode) the kernels return at once and the outputs are meaningless, as dgs_backward's are: the caller
+ * discards the step (skip_flag).  Always one launch chain on `stream`: the context's side stream is never used, so the
+ * call can be captured into a graph with no fork. */
+int dgs_backward_pose_only(const DgsProblem* p, const DgsBackwardIO* io, dgs_stream_t stream);
 /* Replaces Rasterizer::markVisible (rasterizer_impl.cu:141-153); present is bool[P] as bytes. */
 int dgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, dgs_stream_t stream);
@@ -490,6 +506,50 @@ int dgs_pose_forward(const float* ctrl_trans, const float* ctrl_rot, const float
 int dgs_pose_backward(const float* ctrl_trans, const float* ctrl_rot, const float* nu, const float* proj, int32_t C,
                       int32_t K, int32_t quaternion, const float* dL_dview, const float* dL_dfull, void* scratch,
                       float* dL_dctrl_trans, float* dL_dctrl_rot, float* dL_dnu, dgs_stream_t stream);
+
+/* ---- evaluation protocol (ABI 15; test.py:72-186 of the reference) ------------------------------------------------
+ * The pose chain of the test-view fit for ONE view (OptimPoseModel.forward, test.py:72-91): rot [n,4] quaternions in
+ * (x, y, z, w) order, trans [n,3];  q = rot[idx] + 1e-8, unit quaternion, rotation matrix (the arithmetic of the
+ * "quarternion_cartesian" curve of dgs_pose_forward), world_view[:3,:3] = R, world_view[3,:3] = trans[idx],
+ * full_proj = world_view @ proj (proj: the transposed projection matrix, as for dgs_pose_forward),
+ * camera_center = inverse(world_view)[3,:3].  Outputs view / full [4,4], campos [3].  The view's index is read from
+ * device memory when the kernel runs (idx_dev, one int32; a captured step serves every view) or, with idx_dev = NULL,
+ * taken from `idx`; a device-side index outside [0, n) selects view 0.
+ * Backward: dL/d{world_view, full_proj} -> dL_drot [n,4], dL_dtrans [n,3], FULLY written: row idx receives the gradient,
+ * every other row zeros (the dense gradient torch leaves on an indexed parameter, which a dense Adam then consumes).  The
+ * camera centre carries no gradient (the rasteriser returns none for campos). */
+int dgs_testpose_forward(const float* rot, const float* trans, const int32_t* idx_dev, int32_t idx, int32_t n,
+                         const float* proj, float* view, float* full, float* campos, dgs_stream_t stream);
+int dgs_testpose_backward(const float* rot, const float* trans, const int32_t* idx_dev, int32_t idx, int32_t n,
+                          const float* proj, const float* dL_dview, const float* dL_dfull, float* dL_drot,
+                          float* dL_dtrans, dgs_stream_t stream);
+
+/* The loss of one step of that fit (test.py:171-178) for one image x [C,HW]:
+ *   y = clamp(tone_map(x), 0, 1);  l1 = mean |y - gt|;  mse = mean (y - gt)^2;  dL_dx = upstream * d l1 / dx
+ * tone_map: DGS_TONE_IDENTITY, or DGS_TONE_GAMMA = max((x - bound) / (1 - 2 bound), eps) ^ (1 / 2.2) (scene/tonemapping.py).
+ * Derivative conventions are torch's: clamp and clamp_min pass the gradient where the input is inside or ON the bound,
+ * sign(0) = 0.  gt: the image (n_gt = 1, gt_index_dev = NULL), or with gt_index_dev (one device int32, read when the
+ * kernel runs) image gt_index_dev[0] of a stack [n_gt,C,HW]; an index outside [0, n_gt) selects image 0, as an index
+ * outside [0, n) selects view 0 in dgs_testpose_*: nothing is read out of bounds.  upstream: optional device scalar (NULL = 1).  dL_dx [C,HW] and `work` are each optional (not both
+ * NULL).  work: a 12-word (48-byte, 8-byte aligned) area -- [0] l1, [1] mse as fp32, words [8..9] / [10..11] the same two
+ * values as fp64, the rest scratch of the deterministic fixed-point totals (same scheme and the same NaN rule as
+ * dgs_blur_loss_grad).  l2_ema (optional device float, needs work): l2_ema = 0.6 l2_ema + 0.4 mse, the reference's
+ * l2_error_ema, kept on the device; left alone when skip_flag (optional, see dgs_forward) is non-zero. */
+#define DGS_TONE_IDENTITY 0
+#define DGS_TONE_GAMMA 1
+int dgs_view_loss_grad(const float* x, const float* gt, const int32_t* gt_index_dev, int32_t n_gt, int32_t C, int32_t HW,
+                       int32_t tone_mapping, float eps, float bound, const float* upstream, float* dL_dx, float* work,
+                       float* l2_ema, const uint32_t* skip_flag, dgs_stream_t stream);
+
+/* PSNR and SSIM of two [3,H,W] images as the reference's evaluation computes them (test.py:118-119):
+ * out[0] = mean over the three channels of 20 log10(1 / sqrt(mse_c)) (utils/image_utils.py:17-19),
+ * out[1] = mean of the SSIM map with the 11 x 11 Gaussian window, sigma 1.5, zero padding, per channel
+ * (utils/loss_utils.py:23-63).  Forward only; one launch over 16 x 16 tiles (separable window through LDS, fp64
+ * arithmetic) plus a reduction in block order: deterministic.  tmp >= dgs_image_metrics_tmp_bytes(W, H).  `out` is FIVE
+ * floats: the two values above, then the three per-channel PSNRs out[0] is the mean of.  Identical images give
+ * {+inf, 1, +inf, +inf, +inf}. */
+size_t dgs_image_metrics_tmp_bytes(int32_t W, int32_t H);
+int dgs_image_metrics(const float* a, const float* b, int32_t W, int32_t H, void* tmp, float* out, dgs_stream_t stream);
 
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters

@@ -5,9 +5,9 @@ set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $root/variants/obj_$name
-declare -A extra=( [preprocess]="-ffp-contract=off" [binning]="-ffp-contract=off" [composite]="-fno-slp-vectorize" [optim]="-ffp-contract=off" )
+declare -A extra=( [preprocess]="-ffp-contract=off" [binning]="-ffp-contract=off" [composite]="-fno-slp-vectorize" [optim]="-ffp-contract=off" [metrics]="-ffp-contract=off" )
 objs=""
-for o in preprocess binning composite geometry_bwd pose knn optim api; do
+for o in preprocess binning composite geometry_bwd pose knn optim api metrics; do
   /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function \
     ${extra[$o]} "$@" -c $root/deblurgs_amd/csrc/$o.hip -o $root/variants/obj_$name/$o.o &
   objs="$objs $root/variants/obj_$name/$o.o"

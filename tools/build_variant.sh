@@ -5,7 +5,7 @@ set -e
 name=$1; unit=$2; src=$3; shift 3
 root=$(cd "$(dirname "$0")/.." && pwd)
 obj=$root/deblurgs_amd/csrc/obj
-declare -A extra=( [preprocess]="-ffp-contract=off" [binning]="-ffp-contract=off" [composite]="-fno-slp-vectorize" [optim]="-ffp-contract=off" )
+declare -A extra=( [preprocess]="-ffp-contract=off" [binning]="-ffp-contract=off" [composite]="-fno-slp-vectorize" [optim]="-ffp-contract=off" [metrics]="-ffp-contract=off" )
 base=${unit%.hip}
 mkdir -p $root/variants/obj
 cp "$src" $root/deblurgs_amd/csrc/_variant_$base.hip
@@ -13,7 +13,7 @@ cp "$src" $root/deblurgs_amd/csrc/_variant_$base.hip
   -c $root/deblurgs_amd/csrc/_variant_$base.hip -o $root/variants/obj/${name}_$base.o
 rm -f $root/deblurgs_amd/csrc/_variant_$base.hip
 objs=""
-for o in preprocess binning composite geometry_bwd pose knn optim api; do
+for o in preprocess binning composite geometry_bwd pose knn optim api metrics; do
   if [ "$o" == "$base" ]; then objs="$objs $root/variants/obj/${name}_$base.o"; else objs="$objs $obj/$o.o"; fi
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $root/variants/libdgs_$name.so $objs
