@@ -1,6 +1,8 @@
-// api.hip -- the extern "C" surface of libdgs_hip.so (include/dgs_hip.h): argument checks, blob carving,
-// stage sequencing (replaces Rasterizer::forward / ::backward, rasterizer_impl.cu:198-463, and the torch glue
-// in rasterize_points.cu:35-239), stage timing and the fused loss-gradient image kernel.
+// api.hip -- the rasteriser's part of the extern "C" surface of libdgs_hip.so (include/dgs_hip.h): argument checks, blob
+// carving, stage sequencing (replaces Rasterizer::forward / ::backward, rasterizer_impl.cu:198-463, and the torch glue
+// in rasterize_points.cu:35-239), the backward in parts, contexts and stage timing.  Host code only: every kernel lives in
+// the file of its stage (the image-space loss kernels in loss.hip), and the other files report errors through
+// dgs_fail_arg / dgs_fail_hip below.
 #include <stdio.h>
 #include <string.h>
 
@@ -31,53 +33,55 @@ int sort_bits_for(int W, int H, int K) {
 }
 
 // forward_only: the image blob holds the tile ranges alone (final_T / n_contrib are not stored: offsets 0, size 0)
-void make_layout(int P, int W, int H, int K, uint64_t R, bool wide_records, DgsLayout* L, bool forward_only = false) {
+DgsLayout make_layout(int P, int W, int H, int K, uint64_t R, bool wide_records, bool forward_only = false) {
+  DgsLayout L = {};
   const size_t KP = (size_t)K * (size_t)P;
   const size_t N = (size_t)W * (size_t)H;
   const size_t T = (size_t)((W + DGS_TILE - 1) / DGS_TILE) * (size_t)((H + DGS_TILE - 1) / DGS_TILE);
   size_t o = 0;
-  L->geom_rows = o;      o += up(KP * sizeof(DgsRow));
-  L->cov3D = o;          o += up((size_t)P * 6 * 4);
-  L->pre_sigmoid = o;    o += up(KP * 3 * 4);
-  L->tiles_touched = o;  o += up(KP * 4);
-  L->point_offsets = o;  o += up(KP * 4);
-  L->scan_tmp = o;       o += up(dgs_scan_tmp_words(KP) * 4);
-  L->num_rendered = o;   o += up(32);
-  L->gsort_keys = o;     o += up(KP * 4);
-  L->gsort_keys_alt = o; o += up(KP * 4);
-  L->gsort_vals = o;     o += up(KP * 4);
-  L->gsort_vals_alt = o; o += up(KP * 4);
-  L->tt_sorted = o;      o += up(KP * 4);
-  L->offs_sorted = o;    o += up(KP * 4);
-  L->tt_tight = o;       o += up(KP * 4);
-  L->offs_tight = o;     o += up(KP * 4);
-  L->gsort_tmp = o;      o += up(dgs_depth_sort_tmp_words(K, (uint32_t)P) * 4);
-  L->cull_rec = o;       o += up(KP * 16);
-  L->cull_cnt = o;       o += up(KP * 4);
-  L->geom_total = o;
+  L.geom_rows = o;      o += up(KP * sizeof(DgsRow));
+  L.cov3D = o;          o += up((size_t)P * 6 * 4);
+  L.pre_sigmoid = o;    o += up(KP * 3 * 4);
+  L.tiles_touched = o;  o += up(KP * 4);
+  L.point_offsets = o;  o += up(KP * 4);
+  L.scan_tmp = o;       o += up(dgs_scan_tmp_words(KP) * 4);
+  L.num_rendered = o;   o += up(32);
+  L.gsort_keys = o;     o += up(KP * 4);
+  L.gsort_keys_alt = o; o += up(KP * 4);
+  L.gsort_vals = o;     o += up(KP * 4);
+  L.gsort_vals_alt = o; o += up(KP * 4);
+  L.tt_sorted = o;      o += up(KP * 4);
+  L.offs_sorted = o;    o += up(KP * 4);
+  L.tt_tight = o;       o += up(KP * 4);
+  L.offs_tight = o;     o += up(KP * 4);
+  L.gsort_tmp = o;      o += up(dgs_depth_sort_tmp_words(K, (uint32_t)P) * 4);
+  L.cull_rec = o;       o += up(KP * 16);
+  L.cull_cnt = o;       o += up(KP * 4);
+  L.geom_total = o;
   o = 0;
-  L->final_T = o;        o += forward_only ? 0 : up((size_t)K * N * 4);
-  L->n_contrib = o;      o += forward_only ? 0 : up((size_t)K * N * 4);
-  L->ranges = o;         o += up((size_t)K * T * 8);
-  L->image_total = o;
+  L.final_T = o;        o += forward_only ? 0 : up((size_t)K * N * 4);
+  L.n_contrib = o;      o += forward_only ? 0 : up((size_t)K * N * 4);
+  L.ranges = o;         o += up((size_t)K * T * 8);
+  L.image_total = o;
   o = 0;
-  L->keys_sorted = o;    o += up(R * 8);
-  L->point_list = o;     o += up(R * 4);
-  L->keys_unsorted = o;  o += up(R * 8);
-  L->vals_unsorted = o;  o += up(R * 4);
-  L->sort_tmp = o;       o += up(dgs_sort_tmp_words(R) * 4);
-  L->binning_total = o;
-  L->sort_bits = sort_bits_for(W, H, K);
-  L->sort_passes = dgs_sort_num_passes(32, L->sort_bits);
+  L.keys_sorted = o;    o += up(R * 8);
+  L.point_list = o;     o += up(R * 4);
+  L.keys_unsorted = o;  o += up(R * 8);
+  L.vals_unsorted = o;  o += up(R * 4);
+  L.sort_tmp = o;       o += up(dgs_sort_tmp_words(R) * 4);
+  L.binning_total = o;
+  L.sort_bits = sort_bits_for(W, H, K);
+  L.sort_passes = dgs_sort_num_passes(32, L.sort_bits);
   // compact keys (tile_cull only): tile | Gaussian | emission index in one 64-bit word when the three fit
   const bool compact = !wide_records;   // DgsProblem.wide_records: keep key + value arrays
   const int u_bits = (int)dgs_higher_msb64(R), g_bits = (int)dgs_higher_msb((uint32_t)(P > 0 ? P : 1));
-  L->pack_g_shift = 0;
-  L->pack_tile_shift = 0;
-  if (compact && R > 0 && u_bits + g_bits + (L->sort_bits - 32) <= 64) {
-    L->pack_g_shift = u_bits;
-    L->pack_tile_shift = u_bits + g_bits;
+  L.pack_g_shift = 0;
+  L.pack_tile_shift = 0;
+  if (compact && R > 0 && u_bits + g_bits + (L.sort_bits - 32) <= 64) {
+    L.pack_g_shift = u_bits;
+    L.pack_tile_shift = u_bits + g_bits;
   }
+  return L;
 }
 
 // need_opacity = false: the backward of activated-value problems (raw_params = 0) -- the reference's backward entry point
@@ -95,11 +99,9 @@ int check_problem(const DgsProblem* p, bool need_opacity = true) {
     return fail(DGS_E_ARG, "means3D / opacities are null");
   if ((p->shs == nullptr) == (p->colors_precomp == nullptr))
     return fail(DGS_E_ARG, "Please provide excatly one of either SHs or precomputed colors!");
-  const bool sr = (p->scales != nullptr) && (p->rotations != nullptr);
   if (((p->scales == nullptr || p->rotations == nullptr) && p->cov3D_precomp == nullptr) ||
       ((p->scales != nullptr || p->rotations != nullptr) && p->cov3D_precomp != nullptr))
     return fail(DGS_E_ARG, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-  (void)sr;
   if (p->shs != nullptr && p->M < (p->D + 1) * (p->D + 1)) return fail(DGS_E_ARG, "M < (D+1)^2");
   if (p->raw_params != 0 && p->raw_params != 1 && p->raw_params != 3)
     return fail(DGS_E_ARG, "raw_params must be 0, 1 or 3 (1 | isotropic scale)");
@@ -116,7 +118,7 @@ int check_problem(const DgsProblem* p, bool need_opacity = true) {
   return DGS_OK;
 }
 
-DgsView make_view(const DgsProblem* p) {
+DgsView make_view(const DgsProblem* p, const DgsLayout& L) {
   DgsView v;
   v.P = p->P; v.D = p->D; v.M = p->M; v.W = p->W; v.H = p->H; v.K = p->K;
   v.gx = (p->W + DGS_TILE - 1) / DGS_TILE;
@@ -131,8 +133,8 @@ DgsView make_view(const DgsProblem* p) {
   v.tile_cull = p->tile_cull != 0;
   v.raw_params = (p->raw_params & 1) != 0;
   v.iso_scale = (p->raw_params & 2) != 0;
-  v.pack_g_shift = 0;      // set from the layout by the callers that know R (tile_cull only)
-  v.pack_tile_shift = 0;
+  v.pack_g_shift = v.tile_cull ? L.pack_g_shift : 0;      // (both 0 in a layout made without R)
+  v.pack_tile_shift = v.tile_cull ? L.pack_tile_shift : 0;
   v.scale_lb = p->scale_lb;
   return v;
 }
@@ -169,6 +171,50 @@ void carve(const DgsProblem* p, const DgsLayout& L, DgsCarve* c) {
   c->sort_tmp = b ? reinterpret_cast<uint32_t*>(b + L.sort_tmp) : nullptr;
 }
 
+// DgsBackwardIO.scratch: contribution rows [R], their per-pair totals by natural index [K*P] (64 bytes each), the
+// pose-gradient partials (f64)
+struct ScratchLayout {
+  size_t sums, partials, total;
+};
+ScratchLayout scratch_layout(uint64_t R, int P, int K) {
+  const size_t sums = up((size_t)R * DGS_CONTRIB_F * 4);
+  const size_t partials = sums + up((size_t)K * (size_t)P * DGS_SUMS_F * 4);
+  return {sums, partials, partials + up((size_t)dgs_geometry_bwd_blocks(P) * (size_t)K * 24 * 8) + ALIGN};
+}
+
+// What a call with P > 0 works on: the blob layout for its R, the carved pointers, the kernels' view of the problem and,
+// for a backward, the three parts of its scratch.
+struct Call {
+  DgsLayout L;
+  DgsCarve c;
+  DgsView v;
+  float* contrib = nullptr;
+  float* sums = nullptr;
+  double* partials = nullptr;
+};
+enum { NEED_IMAGE = 1, NEED_BINNING = 2 };
+// Fills `k` for a layout sized by R and checks the caller's capacities: geom_state always, image_state / binning_state
+// (the latter only when R > 0) as `need` says, the scratch of `io` when one is given.  Touches no HIP call.
+int prepare(const DgsProblem* p, uint64_t R, int need, const DgsBackwardIO* io, Call* k) {
+  k->L = make_layout(p->P, p->W, p->H, p->K, R, p->wide_records != 0, p->forward_only != 0);
+  if (p->geom_state == nullptr || p->geom_bytes < k->L.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
+  if ((need & NEED_IMAGE) && (p->image_state == nullptr || p->image_bytes < k->L.image_total))
+    return fail(DGS_E_CAPACITY, "image_state too small");
+  if ((need & NEED_BINNING) && R > 0 && (p->binning_state == nullptr || p->binning_bytes < k->L.binning_total))
+    return fail(DGS_E_CAPACITY, "binning_state too small");
+  carve(p, k->L, &k->c);
+  k->v = make_view(p, k->L);
+  if (io != nullptr) {
+    const ScratchLayout sl = scratch_layout(R, p->P, p->K);
+    if (io->scratch == nullptr || io->scratch_bytes < sl.total) return fail(DGS_E_CAPACITY, "backward scratch too small");
+    char* base = reinterpret_cast<char*>(io->scratch);
+    k->contrib = reinterpret_cast<float*>(base);
+    k->sums = reinterpret_cast<float*>(base + sl.sums);
+    k->partials = reinterpret_cast<double*>(base + sl.partials);
+  }
+  return DGS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ context
 // Everything that outlives a call lives here, owned by the caller (include/dgs_hip.h, ABI 14): the side stream + events of
 // the backward in parts (created on first use, on the device that is current then), its policy, the stage timers.
@@ -202,16 +248,16 @@ int prof_begin(DgsContext* ctx, int stage, hipStream_t s) {
   if (pr.n >= PROF_MAX) return -1;
   const int i = pr.n++;
   if (i >= pr.created) {
-    hipEventCreate(&pr.beg[i]);
-    hipEventCreate(&pr.end[i]);
+    (void)hipEventCreate(&pr.beg[i]);
+    (void)hipEventCreate(&pr.end[i]);
     pr.created = i + 1;
   }
   pr.stage[i] = stage;
-  hipEventRecord(pr.beg[i], s);
+  (void)hipEventRecord(pr.beg[i], s);
   return i;
 }
 void prof_end(DgsContext* ctx, int i, hipStream_t s) {
-  if (i >= 0) hipEventRecord(ctx->prof.end[i], s);
+  if (i >= 0) (void)hipEventRecord(ctx->prof.end[i], s);
 }
 
 struct StageTimer {
@@ -236,346 +282,9 @@ struct StageTimer {
     }                                                                       \
   } while (0)
 
-// --------------------------------------------------------------------------- fused loss-gradient image (f1)
-// train.py:143-165 with utils/loss_utils.py:17-18 (l1_loss) and :80-93 (batchwise_smoothness_loss):
-//   blur = mean_k sub_k;  L = mean|blur - gt| + lambda_t * mean|sub_{k+1} - sub_k|
-//   dL/dsub_k = sign(blur-gt)/(E*K) + lambda_t * [sign(sub_k - sub_{k-1}) - sign(sub_{k+1} - sub_k)] / (E*(K-1))
-// with E = C*H*W.  One thread per (channel, pixel) element; replaces ~20 elementwise launches and ~1.5 GB of
-// traffic between the fused forward and backward.
-__device__ __forceinline__ float sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
-
-// Deterministic totals: a block's two sums (fixed-order fp32 trees of non-negative terms) are added as 2^-24 fixed-point
-// integers -- integer addition is associative, so the result does not depend on the order in which the blocks arrive,
-// unlike float atomics -- and the last block to arrive converts them.  losses is an 8-word work area: [0] L1,
-// [1] smoothness, [2..3] / [4..5] the two 64-bit accumulators, [6] arrival counter, [7] sticky "not representable" flag
-// (all zeroed by the launcher).  The fixed point covers totals below 2^40 ~ 1.1e12 at a resolution far below the fp32
-// rounding of the block sums; a block sum that is NaN / Inf (a diverged render, a NaN in the ground truth) or a total that
-// leaves the range sets the flag and both losses come back NaN, as float arithmetic would have reported them.
-__device__ __forceinline__ void loss_totals_publish(float a, float c, float* __restrict__ losses, size_t E, int K) {
-  constexpr double FX = 16777216.0;   // 2^24
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(losses + 2);
-  unsigned int* flag = reinterpret_cast<unsigned int*>(losses + 7);
-  const bool fin = __builtin_isfinite(a) && __builtin_isfinite(c) && a < 5.0e11f && c < 5.0e11f;
-  if (!fin) {
-    atomicOr(flag, 1u);
-  } else {
-    const unsigned long long ia = (unsigned long long)__double2ll_rn((double)a * FX);
-    const unsigned long long ic = (unsigned long long)__double2ll_rn((double)c * FX);
-    const unsigned long long oa = atomicAdd(&acc[0], ia), oc = atomicAdd(&acc[1], ic);
-    if (oa + ia < oa || oc + ic < oc) atomicOr(flag, 1u);   // the 64-bit accumulator wrapped
-  }
-  __threadfence();
-  const unsigned int ticket = atomicAdd(reinterpret_cast<unsigned int*>(losses + 6), 1u);
-  if (ticket == gridDim.x - 1) {
-    __threadfence();
-    const unsigned long long t0 = atomicAdd(&acc[0], 0ull), t1 = atomicAdd(&acc[1], 0ull);
-    const bool bad = atomicOr(flag, 0u) != 0u;
-    const float nanv = __int_as_float(0x7fc00000);
-    losses[0] = bad ? nanv : (float)(((double)t0 / FX) / (double)E);
-    losses[1] = bad ? nanv : ((K > 1) ? (float)(((double)t1 / FX) / ((double)E * (double)(K - 1))) : 0.0f);
-  }
-}
-
-// MODE 0: blur + loss values (forward).  MODE 1: dL/dsubframes, multiplied by the upstream scalar *scale read
-// from device memory (backward; no host sync, no extra elementwise pass over [K,3,H,W]).  MODE 2: both at once.
-template <int MODE, int V>  // V = elements per thread (4 -> 16-byte loads/stores when E % 4 == 0, else 1)
-__global__ void __launch_bounds__(256)
-blur_loss_kernel(const float* __restrict__ sub, const float* __restrict__ gt, int K, size_t E, float lambda_t,
-                 const float* __restrict__ lambda_dev, const float* __restrict__ scale, float* __restrict__ blur,
-                 float* __restrict__ dsub, float* __restrict__ losses) {
-  if (lambda_dev != nullptr) lambda_t = lambda_dev[0];   // graph replay: the scheduled weight lives in device memory
-  __shared__ float red[2][4];
-  typedef float vec __attribute__((ext_vector_type(V)));
-  float l1 = 0.0f, sm = 0.0f;
-  // grid-stride loop: the launcher caps the grid (the loss totals cost three same-address atomics per block)
-  for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; e < E; e += (size_t)gridDim.x * 256 * V) {
-    auto ld = [](const float* p) { return *reinterpret_cast<const vec*>(p); };
-    if (MODE == 0) {
-      // forward: ONE pass over the K subframes (sum for the blur and the adjacent differences together), unrolled so
-      // that several 16-byte loads per lane are in flight
-      vec prev = ld(sub + e);
-      vec acc = prev;
-#pragma unroll 4
-      for (int k = 1; k < K; k++) {
-        const vec nxt = ld(sub + (size_t)k * E + e);
-        const vec dd = nxt - prev;
-        acc += nxt;
-#pragma unroll
-        for (int i = 0; i < V; i++) sm += fabsf(dd[i]);
-        prev = nxt;
-      }
-      const vec b = acc / (float)K;
-      *reinterpret_cast<vec*>(blur + e) = b;
-      const vec d = b - ld(gt + e);
-#pragma unroll
-      for (int i = 0; i < V; i++) l1 += fabsf(d[i]);
-    } else {
-      vec b;
-      if (MODE == 1 && blur != nullptr) {
-        b = ld(blur + e);   // backward: the forward's blur is handed back in, no second summation
-      } else {
-        vec acc = ld(sub + e);
-#pragma unroll 4
-        for (int k = 1; k < K; k++) acc += ld(sub + (size_t)k * E + e);
-        b = acc / (float)K;
-        if (MODE == 2) *reinterpret_cast<vec*>(blur + e) = b;
-      }
-      const vec d = b - ld(gt + e);
-      const float up = (scale != nullptr) ? scale[0] : 1.0f;
-      const float c_l1 = up / ((float)E * (float)K);
-      const float ws = (K > 1) ? up * lambda_t / ((float)E * (float)(K - 1)) : 0.0f;
-      vec g_l1;
-#pragma unroll
-      for (int i = 0; i < V; i++) {
-        l1 += fabsf(d[i]);
-        g_l1[i] = c_l1 * sgn(d[i]);
-      }
-      vec prev = ld(sub + e);
-      vec s_prev = (vec)(0.0f);  // sign(x_k - x_{k-1})
-#pragma unroll 4
-      for (int k = 0; k < K; k++) {
-        vec s_next = (vec)(0.0f);
-        vec nxt = prev;
-        if (k + 1 < K) {
-          nxt = ld(sub + (size_t)(k + 1) * E + e);
-          const vec dd = nxt - prev;
-#pragma unroll
-          for (int i = 0; i < V; i++) {
-            sm += fabsf(dd[i]);
-            s_next[i] = sgn(dd[i]);
-          }
-        }
-        *reinterpret_cast<vec*>(dsub + (size_t)k * E + e) = g_l1 + ws * (s_prev - s_next);
-        s_prev = s_next;
-        prev = nxt;
-      }
-    }
-  }
-  if (MODE == 1) return;
-  l1 = dgs_wave_sum63(l1);
-  sm = dgs_wave_sum63(sm);
-  const int lane = dgs_lane(), w = threadIdx.x >> 6;
-  if (lane == 63) {
-    red[0][w] = l1;
-    red[1][w] = sm;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const float c = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    loss_totals_publish(a, c, losses, E, K);
-  }
-}
-
-// Forward + backward at once (MODE 2's results, bit for bit) for K <= KMAX with the K subframe values of an element
-// held in registers: every subframe value is read ONCE (MODE 2 streams the subframes twice: 1.1 GB instead of 0.77 GB
-// at the metric configuration).
-template <int KMAX, int V>
-__global__ void __launch_bounds__(256)
-blur_loss_all_kernel(const float* __restrict__ sub, const float* __restrict__ gt, int K, size_t E, float lambda_t,
-                     const float* __restrict__ lambda_dev, const float* __restrict__ scale, float* __restrict__ blur,
-                     float* __restrict__ dsub, float* __restrict__ losses) {
-  if (lambda_dev != nullptr) lambda_t = lambda_dev[0];
-  __shared__ float red[2][4];
-  typedef float vec __attribute__((ext_vector_type(V)));
-  float l1 = 0.0f, sm = 0.0f;
-  for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; e < E; e += (size_t)gridDim.x * 256 * V) {
-    vec x[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; k++)
-      if (k < K) x[k] = *reinterpret_cast<const vec*>(sub + (size_t)k * E + e);
-    vec acc = x[0];
-#pragma unroll
-    for (int k = 1; k < KMAX; k++)
-      if (k < K) acc += x[k];
-    const vec b = acc / (float)K;
-    *reinterpret_cast<vec*>(blur + e) = b;
-    const vec d = b - *reinterpret_cast<const vec*>(gt + e);
-    const float up = (scale != nullptr) ? scale[0] : 1.0f;
-    const float c_l1 = up / ((float)E * (float)K);
-    const float ws = (K > 1) ? up * lambda_t / ((float)E * (float)(K - 1)) : 0.0f;
-    vec g_l1;
-#pragma unroll
-    for (int i = 0; i < V; i++) {
-      l1 += fabsf(d[i]);
-      g_l1[i] = c_l1 * sgn(d[i]);
-    }
-    vec s_prev = (vec)(0.0f);
-#pragma unroll
-    for (int k = 0; k < KMAX; k++) {
-      if (k < K) {
-        vec s_next = (vec)(0.0f);
-        if (k + 1 < K) {
-          const vec dd = x[k + 1 < KMAX ? k + 1 : k] - x[k];
-#pragma unroll
-          for (int i = 0; i < V; i++) {
-            sm += fabsf(dd[i]);
-            s_next[i] = sgn(dd[i]);
-          }
-        }
-        *reinterpret_cast<vec*>(dsub + (size_t)k * E + e) = g_l1 + ws * (s_prev - s_next);
-        s_prev = s_next;
-      }
-    }
-  }
-  l1 = dgs_wave_sum63(l1);
-  sm = dgs_wave_sum63(sm);
-  const int lane = dgs_lane(), w = threadIdx.x >> 6;
-  if (lane == 63) {
-    red[0][w] = l1;
-    red[1][w] = sm;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {   // deterministic fixed-point totals
-    const float a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const float c = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    loss_totals_publish(a, c, losses, E, K);
-  }
-}
-
-// The loss block of ONE RANK of a subframe-sharded view (deblurgs_amd/sharding.py; new work: the reference is
-// single-GPU).  The rank holds Kl consecutive subframes of the view's K; `blur` is the view's blur image (mean over all K
-// subframes: the ranks' partial sums were all-reduced), prev / next the neighbouring ranks' boundary subframes (NULL at
-// the ends of the view).  Same arithmetic as blur_loss_all_kernel for the subframes held here:
-//   dL/dsub_k = sign(blur - gt) / (E K) + lambda_t [sign(sub_k - sub_{k-1}) - sign(sub_{k+1} - sub_k)] / (E (K - 1)),
-// losses[0] = mean |blur - gt| (the same on every rank), losses[1] = this rank's share of the smoothness value: the
-// differences whose LEFT frame it holds, / (E (K - 1)) -- the caller sums the shares over the ranks.
-template <int KMAX, int V>
-__global__ void __launch_bounds__(256)
-blur_loss_slice_kernel(const float* __restrict__ sub, const float* __restrict__ prev, const float* __restrict__ next,
-                       const float* __restrict__ blur, const float* __restrict__ gt, int Kl, int K, size_t E,
-                       float lambda_t, float* __restrict__ dsub, float* __restrict__ losses) {
-  __shared__ float red[2][4];
-  typedef float vec __attribute__((ext_vector_type(V)));
-  float l1 = 0.0f, sm = 0.0f;
-  for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; e < E; e += (size_t)gridDim.x * 256 * V) {
-    vec x[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; k++)
-      if (k < Kl) x[k] = *reinterpret_cast<const vec*>(sub + (size_t)k * E + e);
-    const vec d = *reinterpret_cast<const vec*>(blur + e) - *reinterpret_cast<const vec*>(gt + e);
-    const float c_l1 = 1.0f / ((float)E * (float)K);
-    const float ws = (K > 1) ? lambda_t / ((float)E * (float)(K - 1)) : 0.0f;
-    vec g_l1;
-#pragma unroll
-    for (int i = 0; i < V; i++) {
-      l1 += fabsf(d[i]);
-      g_l1[i] = c_l1 * sgn(d[i]);
-    }
-    vec s_prev = (vec)(0.0f);
-    if (prev != nullptr) {   // the difference across the lower rank boundary belongs to the rank below: sign only
-      const vec dd = x[0] - *reinterpret_cast<const vec*>(prev + e);
-#pragma unroll
-      for (int i = 0; i < V; i++) s_prev[i] = sgn(dd[i]);
-    }
-#pragma unroll
-    for (int k = 0; k < KMAX; k++) {
-      if (k < Kl) {
-        vec s_next = (vec)(0.0f);
-        const bool inner = k + 1 < Kl;
-        if (inner || next != nullptr) {
-          const vec nx = inner ? x[k + 1 < KMAX ? k + 1 : k] : *reinterpret_cast<const vec*>(next + e);
-          const vec dd = nx - x[k];
-#pragma unroll
-          for (int i = 0; i < V; i++) {
-            sm += fabsf(dd[i]);
-            s_next[i] = sgn(dd[i]);
-          }
-        }
-        *reinterpret_cast<vec*>(dsub + (size_t)k * E + e) = g_l1 + ws * (s_prev - s_next);
-        s_prev = s_next;
-      }
-    }
-  }
-  l1 = dgs_wave_sum63(l1);
-  sm = dgs_wave_sum63(sm);
-  const int lane = dgs_lane(), w = threadIdx.x >> 6;
-  if (lane == 63) {
-    red[0][w] = l1;
-    red[1][w] = sm;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {   // deterministic fixed-point totals
-    const float a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const float c = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    loss_totals_publish(a, c, losses, E, K);
-  }
-}
-
-// train.py:188-193 + scene/gaussian_model.py:456-458 for the K subframes of one step, in subframe order
-__global__ void __launch_bounds__(256)
-densify_stats_kernel(const float* __restrict__ vgrad, const int32_t* __restrict__ radii, int K, int K_total, int P,
-                     float* __restrict__ max_radii2D, float* __restrict__ accum, float* __restrict__ denom,
-                     const uint32_t* __restrict__ skip) {
-  if (skip != nullptr && skip[0] != 0u) return;
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= P) return;
-  float mr = max_radii2D[g], ac = accum[g], dn = denom[g];
-  const float inc = (float)(1.0 / (double)K_total);
-  for (int k = 0; k < K; k++) {
-    const size_t o = (size_t)k * P + g;
-    const int r = radii[o];
-    if (r > 0) {
-      mr = fmaxf(mr, (float)r);
-      const float gx = vgrad[3 * o], gy = vgrad[3 * o + 1];
-      ac += sqrtf(gx * gx + gy * gy);
-      dn += inc;
-    }
-  }
-  max_radii2D[g] = mr;
-  accum[g] = ac;
-  denom[g] = dn;
-}
-
 }  // namespace
 
-hipError_t dgs_launch_blur_loss(const float* sub, const float* gt, int K, int C, int HW, float lambda_t,
-                                const float* lambda_dev, const float* scale, float* blur, float* dsub, float* losses,
-                                hipStream_t s) {
-  const size_t E = (size_t)C * HW;
-  if (losses != nullptr) {
-    hipError_t e = dgs_launch_clear_words(reinterpret_cast<uint32_t*>(losses), 8, s);   // results + accumulators + arrival counter
-    if (e != hipSuccess) return e;
-  }
-  const bool v4 = (E % 4 == 0) && ((reinterpret_cast<uintptr_t>(sub) | reinterpret_cast<uintptr_t>(gt) |
-                                    reinterpret_cast<uintptr_t>(blur) | reinterpret_cast<uintptr_t>(dsub)) % 16 == 0);
-  const size_t per = v4 ? 4 : 1;
-  // at most DGS_LOSS_BLOCKS blocks (2 per CU; every thread keeps K 16-byte loads in flight): enough to saturate HBM, few
-  // enough that the per-block same-address atomics of the loss totals (~58 ns per block: 0.35 ms with 6075 blocks at
-  // 1080p, still 0.11 ms of the 800x800 case's kernel with 1875) disappear.  Measured 2048 / 1024 / 512 blocks:
-  // 1.204 / 1.157 / 1.144 ms per cfg2 step, 11.99 / 12.01 / 11.91 ms at the metric config.  The totals depend on the
-  // grid, which is a function of E only -- still bitwise reproducible
-  const size_t want = (E / per + 255) / 256;
-#ifndef DGS_LOSS_BLOCKS
-#define DGS_LOSS_BLOCKS 512
-#endif
-  const dim3 grid((uint32_t)(want < DGS_LOSS_BLOCKS ? (want == 0 ? 1 : want) : DGS_LOSS_BLOCKS));
-#define DGS_BL(MODE)                                                                                              \
-  do {                                                                                                            \
-    if (v4)                                                                                                       \
-      hipLaunchKernelGGL((blur_loss_kernel<MODE, 4>), grid, dim3(256), 0, s, sub, gt, K, E, lambda_t, lambda_dev, scale, blur, \
-                         dsub, losses);                                                                           \
-    else                                                                                                          \
-      hipLaunchKernelGGL((blur_loss_kernel<MODE, 1>), grid, dim3(256), 0, s, sub, gt, K, E, lambda_t, lambda_dev, scale, blur, \
-                         dsub, losses);                                                                           \
-  } while (0)
-  if (dsub == nullptr)
-    DGS_BL(0);
-  else if (losses == nullptr)
-    DGS_BL(1);
-  else if (v4 && K <= 16)
-    hipLaunchKernelGGL((blur_loss_all_kernel<16, 4>), grid, dim3(256), 0, s, sub, gt, K, E, lambda_t, lambda_dev, scale, blur, dsub,
-                       losses);
-  else if (v4 && K <= 32)
-    hipLaunchKernelGGL((blur_loss_all_kernel<32, 2>), grid, dim3(256), 0, s, sub, gt, K, E, lambda_t, lambda_dev, scale, blur, dsub,
-                       losses);
-  else
-    DGS_BL(2);
-#undef DGS_BL
-  return hipGetLastError();
-}
-
-// error reporting for the other translation units of the library (optim.hip)
+// error reporting for the other translation units of the library (dgs_common.h)
 int dgs_fail_arg(const char* msg) { return fail(DGS_E_ARG, "%s", msg); }
 int dgs_fail_hip(hipError_t e, const char* where) { return fail_hip(e, where); }
 
@@ -584,40 +293,24 @@ extern "C" {
 int dgs_abi_version(void) { return DGS_ABI_VERSION; }
 const char* dgs_last_error(void) { return g_err; }
 
-size_t dgs_geom_state_bytes(int32_t P, int32_t K) {
-  DgsLayout L;
-  make_layout(P, 16, 16, K, 0, false, &L);
-  return L.geom_total;
-}
-size_t dgs_image_state_bytes(int32_t W, int32_t H, int32_t K) {
-  DgsLayout L;
-  make_layout(0, W, H, K, 0, false, &L);
-  return L.image_total;
-}
+size_t dgs_geom_state_bytes(int32_t P, int32_t K) { return make_layout(P, 16, 16, K, 0, false).geom_total; }
+size_t dgs_image_state_bytes(int32_t W, int32_t H, int32_t K) { return make_layout(0, W, H, K, 0, false).image_total; }
 size_t dgs_image_state_bytes_forward_only(int32_t W, int32_t H, int32_t K) {
-  DgsLayout L;
-  make_layout(0, W, H, K, 0, false, &L, true);
-  return L.image_total;
+  return make_layout(0, W, H, K, 0, false, true).image_total;
 }
 size_t dgs_binning_state_bytes(uint64_t R, int32_t W, int32_t H, int32_t K) {
-  DgsLayout L;
-  make_layout(0, W, H, K, R, false, &L);
-  return L.binning_total;
+  return make_layout(0, W, H, K, R, false).binning_total;
 }
-size_t dgs_backward_scratch_bytes(uint64_t R, int32_t P, int32_t K) {
-  // contribution rows [R] + their per-pair totals by natural index [K*P] (48 bytes each) + pose-gradient partials (f64)
-  return up((size_t)R * DGS_CONTRIB_F * 4) + up((size_t)K * (size_t)P * DGS_SUMS_F * 4) +
-         up((size_t)dgs_geometry_bwd_blocks(P) * (size_t)K * 24 * 8) + ALIGN;
-}
+size_t dgs_backward_scratch_bytes(uint64_t R, int32_t P, int32_t K) { return scratch_layout(R, P, K).total; }
 int dgs_layout(int32_t P, int32_t W, int32_t H, int32_t K, uint64_t R, int32_t wide_records, DgsLayout* out) {
   if (out == nullptr) return fail(DGS_E_ARG, "null DgsLayout");
-  make_layout(P, W, H, K, R, wide_records != 0, out);
+  *out = make_layout(P, W, H, K, R, wide_records != 0);
   return DGS_OK;
 }
 int dgs_backward_scratch_layout(uint64_t R, int32_t P, int32_t K, size_t* sums_offset, size_t* partials_offset) {
-  const size_t so = up((size_t)R * DGS_CONTRIB_F * 4);
-  if (sums_offset) *sums_offset = so;
-  if (partials_offset) *partials_offset = so + up((size_t)K * (size_t)P * DGS_SUMS_F * 4);
+  const ScratchLayout sl = scratch_layout(R, P, K);
+  if (sums_offset) *sums_offset = sl.sums;
+  if (partials_offset) *partials_offset = sl.partials;
   return DGS_OK;
 }
 
@@ -657,21 +350,17 @@ static int forward_geometry_impl(const DgsProblem* p, const DgsForwardOut* out, 
     return DGS_OK;
   }
   if (out->radii == nullptr) return fail(DGS_E_ARG, "DgsForwardOut: radii is null");
-  DgsLayout L;
-  make_layout(p->P, p->W, p->H, p->K, 0, p->wide_records != 0, &L, p->forward_only != 0);
-  if (p->geom_state == nullptr || p->geom_bytes < L.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
-  DgsCarve c;
-  carve(p, L, &c);
-  const DgsView v = make_view(p);
+  Call k;
+  rc = prepare(p, 0, 0, nullptr, &k);
+  if (rc != DGS_OK) return rc;
+  const DgsCarve& c = k.c;
+  const DgsView& v = k.v;
   hipError_t e = dgs_launch_clear_words(c.num_rendered, 8, s);   // (a kernel, not a memset node: see finalize_count_kernel)
   if (e != hipSuccess) return fail_hip(e, "clear status");
   DGS_STAGE(DGS_STAGE_PREPROCESS, "preprocess", dgs_launch_preprocess(*p, v, c, out->radii, s));
   if (!v.tile_cull) {
     DGS_STAGE(DGS_STAGE_SCAN, "scan",
               dgs_launch_scan(c.tiles_touched, c.point_offsets, (uint64_t)p->K * p->P, c.scan_tmp, c.num_rendered, s));
-    // two words: R and the high half of the 64-bit total (non-zero = the u32 duplicate offsets overflowed)
-    if (copy_count)
-      e = hipMemcpyAsync(out->num_rendered_host, c.num_rendered, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   } else {
     // tile_cull: R is the number of surviving duplicates: per-slot test in natural order, depth ordering (which also
     // lays the per-pair records and counts out in its order), scan of the counts.  Status words [0], [1] stay 0.
@@ -683,10 +372,11 @@ static int forward_geometry_impl(const DgsProblem* p, const DgsForwardOut* out, 
       DGS_STAGE(DGS_STAGE_DEPTH_ORDER, "depth order", launch_depth_order(p, c, s));
       DGS_STAGE(DGS_STAGE_TILE_CULL, "tile cull", launch_tile_cull(v, c, s));
     }
-    // two words: R and the high half of the 64-bit total (non-zero = the u32 duplicate offsets overflowed)
-    if (copy_count)
-      e = hipMemcpyAsync(out->num_rendered_host, c.num_rendered + 2, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   }
+  // two words: R and the high half of the 64-bit total (non-zero = the u32 duplicate offsets overflowed)
+  if (copy_count)
+    e = hipMemcpyAsync(out->num_rendered_host, c.num_rendered + (v.tile_cull ? 2 : 0), 2 * sizeof(uint32_t),
+                       hipMemcpyDeviceToHost, s);
   if (e != hipSuccess) return fail_hip(e, "copy num_rendered");
   return DGS_OK;
 }
@@ -711,19 +401,12 @@ static int forward_render_impl(const DgsProblem* p, const DgsForwardOut* out, ui
     if (e == hipSuccess && out->out_depth != nullptr) e = hipMemsetAsync(out->out_depth, 0, (size_t)p->K * N * 4, s);
     return e == hipSuccess ? DGS_OK : fail_hip(e, "memset outputs");
   }
-  DgsLayout L;
-  make_layout(p->P, p->W, p->H, p->K, R, p->wide_records != 0, &L, p->forward_only != 0);
-  if (p->geom_state == nullptr || p->geom_bytes < L.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
-  if (p->image_state == nullptr || p->image_bytes < L.image_total) return fail(DGS_E_CAPACITY, "image_state too small");
-  if (R > 0 && (p->binning_state == nullptr || p->binning_bytes < L.binning_total))
-    return fail(DGS_E_CAPACITY, "binning_state too small");
-  DgsCarve c;
-  carve(p, L, &c);
-  DgsView v = make_view(p);
-  if (v.tile_cull) {
-    v.pack_g_shift = L.pack_g_shift;
-    v.pack_tile_shift = L.pack_tile_shift;
-  }
+  Call k;
+  rc = prepare(p, R, NEED_IMAGE | NEED_BINNING, nullptr, &k);
+  if (rc != DGS_OK) return rc;
+  const DgsLayout& L = k.L;
+  const DgsCarve& c = k.c;
+  const DgsView& v = k.v;
   const int key_lo = v.pack_tile_shift > 0 ? v.pack_tile_shift : 32;   // first tile bit of the key
   const uint32_t* n_dev = speculative ? c.num_rendered + 4 : nullptr;
   if ((phases & 1) && (R > 0 || v.tile_cull)) {  // tile_cull with R == 0 still marks the visible pairs as "no surviving tile"
@@ -767,22 +450,12 @@ int dgs_forward_render(const DgsProblem* p, const DgsForwardOut* out, uint32_t R
 }
 
 static int forward_capacity_impl(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream,
-                                 int phases);
-int dgs_forward(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream) {
-  return forward_capacity_impl(p, out, capacity, stream, 3);
-}
-int dgs_forward_lists(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream) {
-  return forward_capacity_impl(p, out, capacity, stream, 1);
-}
-int dgs_forward_composite(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream) {
-  return forward_render_impl(p, out, capacity, true, reinterpret_cast<hipStream_t>(stream), 2);
-}
-static int forward_capacity_impl(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream,
                                  int phases) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // The count words reach the host from the finalize kernel itself when num_rendered_host is device-accessible pinned
   // memory (hipHostMalloc / torch pin_memory: the usual case) -- no copy node in the launch chain; otherwise by copies.
   uint32_t* host_dev = nullptr;
+  Call k;
   {   // arguments first: an invalid call is refused before anything touches the HIP runtime
     const int rc0 = check_problem(p);
     if (rc0 != DGS_OK) return rc0;
@@ -790,13 +463,8 @@ static int forward_capacity_impl(const DgsProblem* p, const DgsForwardOut* out, 
       return fail(DGS_E_ARG, "DgsForwardOut: num_rendered_host is null");
     if (p->P > 0) {
       if (out->radii == nullptr) return fail(DGS_E_ARG, "DgsForwardOut: radii is null");
-      DgsLayout L0;
-      make_layout(p->P, p->W, p->H, p->K, capacity, p->wide_records != 0, &L0, p->forward_only != 0);
-      if (p->geom_state == nullptr || p->geom_bytes < L0.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
-      if ((phases & 2) && (p->image_state == nullptr || p->image_bytes < L0.image_total))
-        return fail(DGS_E_CAPACITY, "image_state too small");
-      if (capacity > 0 && (p->binning_state == nullptr || p->binning_bytes < L0.binning_total))
-        return fail(DGS_E_CAPACITY, "binning_state too small");
+      const int rc1 = prepare(p, capacity, ((phases & 2) ? NEED_IMAGE : 0) | NEED_BINNING, nullptr, &k);
+      if (rc1 != DGS_OK) return rc1;
     }
   }
   if (p->P > 0) {
@@ -809,10 +477,7 @@ static int forward_capacity_impl(const DgsProblem* p, const DgsForwardOut* out, 
   int rc = forward_geometry_impl(p, out, stream, host_dev == nullptr);
   if (rc != DGS_OK) return rc;
   if (p->P > 0) {
-    DgsLayout L;
-    make_layout(p->P, p->W, p->H, p->K, 0, p->wide_records != 0, &L, p->forward_only != 0);
-    DgsCarve c;
-    carve(p, L, &c);
+    const DgsCarve& c = k.c;   // (only the status words are used: their place does not depend on the layout's R)
     hipError_t e = dgs_launch_finalize_count(c, p->tile_cull != 0, capacity, out->drop_counter, out->status_dev, host_dev,
                                              out->status_host_indirect, s);
     if (host_dev == nullptr) {
@@ -829,6 +494,15 @@ static int forward_capacity_impl(const DgsProblem* p, const DgsForwardOut* out, 
     out->num_rendered_host[3] = 0;
   }
   return forward_render_impl(p, out, capacity, true, s, phases);
+}
+int dgs_forward(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream) {
+  return forward_capacity_impl(p, out, capacity, stream, 3);
+}
+int dgs_forward_lists(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream) {
+  return forward_capacity_impl(p, out, capacity, stream, 1);
+}
+int dgs_forward_composite(const DgsProblem* p, const DgsForwardOut* out, uint32_t capacity, dgs_stream_t stream) {
+  return forward_render_impl(p, out, capacity, true, reinterpret_cast<hipStream_t>(stream), 2);
 }
 
 // ---- the compositing backward in parts, each part's row totals next to the next part's compositing
@@ -898,21 +572,22 @@ static int bwd_parts(const DgsContextOptions& opt, int K, int* cut, bool force) 
   return n;
 }
 
-static hipError_t backward_composite_overlapped(const DgsProblem* p, const DgsBackwardIO* io, const DgsView& v, const DgsCarve& c,
-                                                float* contrib, float* sums, double* partials, hipStream_t s, const int* cut,
-                                                int n) {
+static hipError_t backward_composite_overlapped(const DgsProblem* p, const DgsBackwardIO* io, const Call& k, hipStream_t s,
+                                                const int* cut, int n) {
+  const DgsCarve& c = k.c;
+  const DgsView& v = k.v;
   DgsContext* ctx = p->context;
   hipStream_t s2 = ctx->s2;
   hipError_t e = hipSuccess;
   bool forked = false;
   for (int i = 0; i < n && e == hipSuccess; i++) {
-    e = dgs_launch_composite_bwd(v, c, p->bg, io->dL_dout_color, io->dL_dout_depth, contrib, s, cut[i], cut[i + 1]);
+    e = dgs_launch_composite_bwd(v, c, p->bg, io->dL_dout_color, io->dL_dout_depth, k.contrib, s, cut[i], cut[i + 1]);
     if (i + 1 < n) {
       if (e == hipSuccess) e = hipEventRecord(ctx->done[i], s);
       if (e == hipSuccess) e = hipStreamWaitEvent(s2, ctx->done[i], 0);
       if (e == hipSuccess) {
         forked = true;
-        e = dgs_launch_geometry_bwd(*p, v, c, *io, contrib, sums, partials, s2, 1, 0, 0, cut[i], cut[i + 1]);
+        e = dgs_launch_geometry_bwd(*p, v, c, *io, k.contrib, k.sums, k.partials, s2, 1, 0, 0, cut[i], cut[i + 1]);
       }
     }
   }
@@ -924,56 +599,57 @@ static hipError_t backward_composite_overlapped(const DgsProblem* p, const DgsBa
     if (j != hipSuccess && e == hipSuccess) e = j;
     if (j != hipSuccess) (void)hipStreamSynchronize(s2);
   }
-  if (e == hipSuccess) e = dgs_launch_geometry_bwd(*p, v, c, *io, contrib, sums, partials, s, 1, 0, 0, cut[n - 1], cut[n]);
+  if (e == hipSuccess) e = dgs_launch_geometry_bwd(*p, v, c, *io, k.contrib, k.sums, k.partials, s, 1, 0, 0, cut[n - 1], cut[n]);
   return e;
+}
+
+// The argument and capacity checks every backward entry point starts with, then its Call.  all_grads: dgs_backward and its
+// parts write every gradient of the cloud and need all the outputs; false: the camera only (dgs_backward_pose_only: the
+// pose matrices).  P == 0: *empty is set -- nothing to launch -- after the matrix gradients were zeroed (if zero_pose).
+static int backward_prepare(const DgsProblem* p, const DgsBackwardIO* io, bool all_grads, bool zero_pose, int32_t g_begin,
+                            int32_t g_end, hipStream_t s, Call* k, bool* empty) {
+  *empty = false;
+  int rc = check_problem(p, p != nullptr && p->raw_params != 0);
+  if (rc != DGS_OK) return rc;
+  if (p->forward_only)
+    return fail(DGS_E_ARG, "%s: the problem is forward_only (nothing was kept for a backward)",
+                all_grads ? "backward" : "backward_pose_only");
+  if (io == nullptr) return fail(DGS_E_ARG, "null DgsBackwardIO");
+  if (io->dL_dviewmatrix == nullptr || io->dL_dprojmatrix == nullptr)
+    return fail(DGS_E_ARG, "dL_dviewmatrix / dL_dprojmatrix are null");
+  if (p->P == 0) {
+    *empty = true;
+    if (!zero_pose) return DGS_OK;
+    hipError_t e = hipMemsetAsync(io->dL_dviewmatrix, 0, (size_t)p->K * 64, s);
+    if (e == hipSuccess) e = hipMemsetAsync(io->dL_dprojmatrix, 0, (size_t)p->K * 64, s);
+    return e == hipSuccess ? DGS_OK : fail_hip(e, "memset grads");
+  }
+  if (!all_grads) {
+    if (io->dL_dout_color == nullptr || io->radii == nullptr)
+      return fail(DGS_E_ARG, "DgsBackwardIO: dL_dout_color / radii are null");
+  } else {
+    if (io->dL_dout_color == nullptr || io->radii == nullptr || io->dL_dmeans3D == nullptr ||
+        (io->dL_dmeans2D == nullptr && io->stats_max_radii2D == nullptr) || io->dL_dcolors == nullptr ||
+        io->dL_dopacity == nullptr || io->dL_dcov3D == nullptr)
+      return fail(DGS_E_ARG, "DgsBackwardIO: a required pointer is null");
+    if (p->shs != nullptr && io->dL_dsh == nullptr) return fail(DGS_E_ARG, "dL_dsh is null");
+    if (p->raw_params && p->M > 1 && io->dL_dsh_rest == nullptr) return fail(DGS_E_ARG, "dL_dsh_rest is null");
+    if (p->scales != nullptr && (io->dL_dscales == nullptr || io->dL_drotations == nullptr))
+      return fail(DGS_E_ARG, "dL_dscales / dL_drotations are null");
+    if (g_begin < 0 || g_end > p->P || g_begin > g_end || (g_begin % 256) != 0)
+      return fail(DGS_E_ARG, "backward: bad Gaussian range (g_begin must be a multiple of 256)");
+  }
+  return prepare(p, io->num_rendered, NEED_IMAGE | NEED_BINNING, io, k);
 }
 
 // which != 0: 1 = compositing backward + per-pair totals, 2 = per-Gaussian kernel for [g_begin, g_end), 4 = pose sums
 static int backward_impl(const DgsProblem* p, const DgsBackwardIO* io, int which, int32_t g_begin, int32_t g_end,
                          hipStream_t s) {
-  int rc = check_problem(p, p != nullptr && p->raw_params != 0);
-  if (rc != DGS_OK) return rc;
-  if (p->forward_only) return fail(DGS_E_ARG, "backward: the problem is forward_only (nothing was kept for a backward)");
-  if (io == nullptr) return fail(DGS_E_ARG, "null DgsBackwardIO");
-  if (io->dL_dviewmatrix == nullptr || io->dL_dprojmatrix == nullptr)
-    return fail(DGS_E_ARG, "dL_dviewmatrix / dL_dprojmatrix are null");
-  if (p->P == 0) {
-    if (!(which & 4)) return DGS_OK;
-    hipError_t e = hipMemsetAsync(io->dL_dviewmatrix, 0, (size_t)p->K * 64, s);
-    if (e == hipSuccess) e = hipMemsetAsync(io->dL_dprojmatrix, 0, (size_t)p->K * 64, s);
-    return e == hipSuccess ? DGS_OK : fail_hip(e, "memset grads");
-  }
-  if (io->dL_dout_color == nullptr || io->radii == nullptr || io->dL_dmeans3D == nullptr ||
-      (io->dL_dmeans2D == nullptr && io->stats_max_radii2D == nullptr) || io->dL_dcolors == nullptr ||
-      io->dL_dopacity == nullptr ||
-      io->dL_dcov3D == nullptr)
-    return fail(DGS_E_ARG, "DgsBackwardIO: a required pointer is null");
-  if (p->shs != nullptr && io->dL_dsh == nullptr) return fail(DGS_E_ARG, "dL_dsh is null");
-  if (p->raw_params && p->M > 1 && io->dL_dsh_rest == nullptr) return fail(DGS_E_ARG, "dL_dsh_rest is null");
-  if (p->scales != nullptr && (io->dL_dscales == nullptr || io->dL_drotations == nullptr))
-    return fail(DGS_E_ARG, "dL_dscales / dL_drotations are null");
-  if (g_begin < 0 || g_end > p->P || g_begin > g_end || (g_begin % 256) != 0)
-    return fail(DGS_E_ARG, "backward: bad Gaussian range (g_begin must be a multiple of 256)");
+  Call k;
+  bool empty;
+  const int rc = backward_prepare(p, io, true, (which & 4) != 0, g_begin, g_end, s, &k, &empty);
+  if (rc != DGS_OK || empty) return rc;
   const uint64_t R = io->num_rendered;
-  DgsLayout L;
-  make_layout(p->P, p->W, p->H, p->K, R, p->wide_records != 0, &L);
-  if (p->geom_state == nullptr || p->geom_bytes < L.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
-  if (p->image_state == nullptr || p->image_bytes < L.image_total) return fail(DGS_E_CAPACITY, "image_state too small");
-  if (R > 0 && (p->binning_state == nullptr || p->binning_bytes < L.binning_total))
-    return fail(DGS_E_CAPACITY, "binning_state too small");
-  if (io->scratch == nullptr || io->scratch_bytes < dgs_backward_scratch_bytes(R, p->P, p->K))
-    return fail(DGS_E_CAPACITY, "backward scratch too small");
-  DgsCarve c;
-  carve(p, L, &c);
-  DgsView v = make_view(p);
-  if (v.tile_cull) {
-    v.pack_g_shift = L.pack_g_shift;
-    v.pack_tile_shift = L.pack_tile_shift;
-  }
-  float* contrib = reinterpret_cast<float*>(io->scratch);
-  float* sums = reinterpret_cast<float*>(reinterpret_cast<char*>(io->scratch) + up((size_t)R * DGS_CONTRIB_F * 4));
-  double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(sums) +
-                                               up((size_t)p->K * (size_t)p->P * DGS_SUMS_F * 4));
   // (with the stage timers on -- dgs_profile_begin -- the two kernels run one after the other: their event pairs then time
   // what they say; so does debug mode, which synchronises after every stage)
   // ... and never inside a stream capture (unless DGS_BWD_OVERLAP=3 asks for it): on this runtime (ROCm 7.2) an executable
@@ -984,7 +660,7 @@ static int backward_impl(const DgsProblem* p, const DgsBackwardIO* io, int which
   DgsContext* ctx = p->context;
   const int omode = ctx != nullptr ? ctx->opt.bwd_overlap : 0;
   std::unique_lock<std::mutex> side_lock;
-  if ((which & 1) && v.tile_cull && !p->debug && omode != 0 && !ctx->prof.on && (R >= BWD_OVERLAP_MIN_PAIRS || omode >= 2)) {
+  if ((which & 1) && k.v.tile_cull && !p->debug && omode != 0 && !ctx->prof.on && (R >= BWD_OVERLAP_MIN_PAIRS || omode >= 2)) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (omode != 3 && hipStreamIsCapturing(s, &cs) != hipSuccess) cs = hipStreamCaptureStatusActive;   // (unknown: stay serial)
     if (cs == hipStreamCaptureStatusNone) parts = bwd_parts(ctx->opt, p->K, cut, omode >= 2);
@@ -998,18 +674,18 @@ static int backward_impl(const DgsProblem* p, const DgsBackwardIO* io, int which
     }
   }
   if (parts > 1) {
-    hipError_t e = backward_composite_overlapped(p, io, v, c, contrib, sums, partials, s, cut, parts);
+    hipError_t e = backward_composite_overlapped(p, io, k, s, cut, parts);
     side_lock.unlock();
     if (e != hipSuccess) return fail_hip(e, "composite backward (parts)");
   } else if (which & 1) {
     DGS_STAGE(DGS_STAGE_COMPOSITE_BWD, "composite backward",
-              dgs_launch_composite_bwd(v, c, p->bg, io->dL_dout_color, io->dL_dout_depth, contrib, s));
+              dgs_launch_composite_bwd(k.v, k.c, p->bg, io->dL_dout_color, io->dL_dout_depth, k.contrib, s));
     DGS_STAGE(DGS_STAGE_CONTRIB_REDUCE, "contribution-row totals",
-              dgs_launch_geometry_bwd(*p, v, c, *io, contrib, sums, partials, s, 1, 0, 0));
+              dgs_launch_geometry_bwd(*p, k.v, k.c, *io, k.contrib, k.sums, k.partials, s, 1, 0, 0));
   }
   if (which & 6)
     DGS_STAGE(DGS_STAGE_GEOMETRY_BWD, "geometry backward",
-              dgs_launch_geometry_bwd(*p, v, c, *io, contrib, sums, partials, s, which & 6, g_begin, g_end));
+              dgs_launch_geometry_bwd(*p, k.v, k.c, *io, k.contrib, k.sums, k.partials, s, which & 6, g_begin, g_end));
   return DGS_OK;
 }
 
@@ -1038,46 +714,16 @@ int dgs_backward_pose(const DgsProblem* p, const DgsBackwardIO* io, dgs_stream_t
 // kernel.  Always one launch chain on `s`: the context's side stream is never used.
 int dgs_backward_pose_only(const DgsProblem* p, const DgsBackwardIO* io, dgs_stream_t stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = check_problem(p, p != nullptr && p->raw_params != 0);
-  if (rc != DGS_OK) return rc;
-  if (p->forward_only)
-    return fail(DGS_E_ARG, "backward_pose_only: the problem is forward_only (nothing was kept for a backward)");
-  if (io == nullptr) return fail(DGS_E_ARG, "null DgsBackwardIO");
-  if (io->dL_dviewmatrix == nullptr || io->dL_dprojmatrix == nullptr)
-    return fail(DGS_E_ARG, "dL_dviewmatrix / dL_dprojmatrix are null");
-  if (p->P == 0) {
-    hipError_t e = hipMemsetAsync(io->dL_dviewmatrix, 0, (size_t)p->K * 64, s);
-    if (e == hipSuccess) e = hipMemsetAsync(io->dL_dprojmatrix, 0, (size_t)p->K * 64, s);
-    return e == hipSuccess ? DGS_OK : fail_hip(e, "memset grads");
-  }
-  if (io->dL_dout_color == nullptr || io->radii == nullptr)
-    return fail(DGS_E_ARG, "DgsBackwardIO: dL_dout_color / radii are null");
-  const uint64_t R = io->num_rendered;
-  DgsLayout L;
-  make_layout(p->P, p->W, p->H, p->K, R, p->wide_records != 0, &L);
-  if (p->geom_state == nullptr || p->geom_bytes < L.geom_total) return fail(DGS_E_CAPACITY, "geom_state too small");
-  if (p->image_state == nullptr || p->image_bytes < L.image_total) return fail(DGS_E_CAPACITY, "image_state too small");
-  if (R > 0 && (p->binning_state == nullptr || p->binning_bytes < L.binning_total))
-    return fail(DGS_E_CAPACITY, "binning_state too small");
-  if (io->scratch == nullptr || io->scratch_bytes < dgs_backward_scratch_bytes(R, p->P, p->K))
-    return fail(DGS_E_CAPACITY, "backward scratch too small");
-  DgsCarve c;
-  carve(p, L, &c);
-  DgsView v = make_view(p);
-  if (v.tile_cull) {
-    v.pack_g_shift = L.pack_g_shift;
-    v.pack_tile_shift = L.pack_tile_shift;
-  }
-  float* contrib = reinterpret_cast<float*>(io->scratch);
-  float* sums = reinterpret_cast<float*>(reinterpret_cast<char*>(io->scratch) + up((size_t)R * DGS_CONTRIB_F * 4));
-  double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(sums) +
-                                               up((size_t)p->K * (size_t)p->P * DGS_SUMS_F * 4));
+  Call k;
+  bool empty;
+  const int rc = backward_prepare(p, io, false, true, 0, 0, s, &k, &empty);
+  if (rc != DGS_OK || empty) return rc;
   DGS_STAGE(DGS_STAGE_COMPOSITE_BWD, "composite backward",
-            dgs_launch_composite_bwd(v, c, p->bg, io->dL_dout_color, io->dL_dout_depth, contrib, s, 0, -1, true));
+            dgs_launch_composite_bwd(k.v, k.c, p->bg, io->dL_dout_color, io->dL_dout_depth, k.contrib, s, 0, -1, true));
   DGS_STAGE(DGS_STAGE_CONTRIB_REDUCE, "contribution-row totals",
-            dgs_launch_geometry_pose_bwd(*p, v, c, *io, contrib, sums, partials, s, 1));
+            dgs_launch_geometry_pose_bwd(*p, k.v, k.c, *io, k.contrib, k.sums, k.partials, s, 1));
   DGS_STAGE(DGS_STAGE_GEOMETRY_BWD, "geometry backward (pose only)",
-            dgs_launch_geometry_pose_bwd(*p, v, c, *io, contrib, sums, partials, s, 2));
+            dgs_launch_geometry_pose_bwd(*p, k.v, k.c, *io, k.contrib, k.sums, k.partials, s, 2));
   return DGS_OK;
 }
 
@@ -1139,60 +785,6 @@ int dgs_depth_order(uint32_t* keys, uint32_t* keys_alt, uint32_t* order, uint32_
   return e == hipSuccess ? DGS_OK : fail_hip(e, "depth_order");
 }
 
-static int blur_loss_impl(const float* subframes, const float* gt, int32_t K, int32_t C, int32_t HW, float lambda_t,
-                          const float* lambda_dev, const float* upstream, float* blur, float* dL_dsubframes, float* losses,
-                          dgs_stream_t stream) {
-  const bool fwd = (blur != nullptr && losses != nullptr);
-  // losses given: blur is an output (forward, or forward + backward when dL_dsubframes is given too);
-  // losses NULL: backward only, blur (optional) is the forward's blur handed back in
-  if (subframes == nullptr || gt == nullptr || K < 1 || C < 1 || HW < 1 || (!fwd && dL_dsubframes == nullptr) ||
-      (losses != nullptr && blur == nullptr))
-    return fail(DGS_E_ARG, "blur_loss_grad: bad argument");
-  hipError_t e = dgs_launch_blur_loss(subframes, gt, K, C, HW, lambda_t, lambda_dev, upstream, blur, dL_dsubframes,
-                                      losses, reinterpret_cast<hipStream_t>(stream));
-  return e == hipSuccess ? DGS_OK : fail_hip(e, "blur_loss_grad");
-}
-int dgs_blur_loss_grad(const float* subframes, const float* gt, int32_t K, int32_t C, int32_t HW, float lambda_t,
-                       const float* upstream, float* blur, float* dL_dsubframes, float* losses, dgs_stream_t stream) {
-  return blur_loss_impl(subframes, gt, K, C, HW, lambda_t, nullptr, upstream, blur, dL_dsubframes, losses, stream);
-}
-int dgs_blur_loss_grad_dev(const float* subframes, const float* gt, int32_t K, int32_t C, int32_t HW,
-                           const float* lambda_t_dev, const float* upstream, float* blur, float* dL_dsubframes,
-                           float* losses, dgs_stream_t stream) {
-  if (lambda_t_dev == nullptr) return fail(DGS_E_ARG, "blur_loss_grad_dev: lambda_t_dev is null");
-  return blur_loss_impl(subframes, gt, K, C, HW, 0.0f, lambda_t_dev, upstream, blur, dL_dsubframes, losses, stream);
-}
-
-int dgs_blur_loss_slice_grad(const float* subframes, const float* prev_last, const float* next_first, const float* blur,
-                             const float* gt, int32_t K_local, int32_t K_total, int32_t C, int32_t HW, float lambda_t,
-                             float* dL_dsubframes, float* losses, dgs_stream_t stream) {
-  if (subframes == nullptr || blur == nullptr || gt == nullptr || dL_dsubframes == nullptr || losses == nullptr ||
-      K_local < 1 || K_total < K_local || K_local > 32 || C < 1 || HW < 1)
-    return fail(DGS_E_ARG, "blur_loss_slice_grad: bad argument (1 <= K_local <= 32, K_local <= K_total)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t E = (size_t)C * HW;
-  hipError_t e = dgs_launch_clear_words(reinterpret_cast<uint32_t*>(losses), 8, s);
-  if (e != hipSuccess) return fail_hip(e, "blur_loss_slice_grad");
-  const uintptr_t align = reinterpret_cast<uintptr_t>(subframes) | reinterpret_cast<uintptr_t>(blur) |
-                          reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(dL_dsubframes) |
-                          reinterpret_cast<uintptr_t>(prev_last) | reinterpret_cast<uintptr_t>(next_first);
-  const bool v4 = (E % 4 == 0) && (align % 16 == 0);
-  const size_t per = v4 ? 4 : 1;
-  const size_t want = (E / per + 255) / 256;
-  const dim3 grid((uint32_t)(want < 512 ? (want == 0 ? 1 : want) : 512));   // (as dgs_launch_blur_loss: few blocks, few atomics)
-#define DGS_BLS(KMAX, V)                                                                                              \
-  hipLaunchKernelGGL((blur_loss_slice_kernel<KMAX, V>), grid, dim3(256), 0, s, subframes, prev_last, next_first, blur, gt, \
-                     K_local, K_total, E, lambda_t, dL_dsubframes, losses)
-  if (v4) {
-    if (K_local <= 4) DGS_BLS(4, 4); else if (K_local <= 16) DGS_BLS(16, 4); else DGS_BLS(32, 2);
-  } else {
-    if (K_local <= 4) DGS_BLS(4, 1); else if (K_local <= 16) DGS_BLS(16, 1); else DGS_BLS(32, 1);
-  }
-#undef DGS_BLS
-  e = hipGetLastError();
-  return e == hipSuccess ? DGS_OK : fail_hip(e, "blur_loss_slice_grad");
-}
-
 // device-side address of a pointer that is either device memory or mapped pinned host memory; nullptr otherwise (pageable)
 static void* device_view(const void* ptr) {
   void* dp = nullptr;
@@ -1217,20 +809,6 @@ int dgs_copy_words(void* dst, const void* src, int32_t n_words, dgs_stream_t str
   else                                 // a pageable end: the runtime's copy
     e = hipMemcpyAsync(dst, src, (size_t)n_words * 4, hipMemcpyDefault, s);
   return e == hipSuccess ? DGS_OK : fail_hip(e, "copy_words");
-}
-
-int dgs_densify_stats(const float* viewspace_grad, const int32_t* radii, int32_t K, int32_t K_total, int32_t P,
-                      float* max_radii2D, float* xyz_gradient_accum, float* denom, const uint32_t* skip_flag,
-                      dgs_stream_t stream) {
-  if (K_total <= 0) K_total = K;
-  if (K < 1 || K_total < K || P < 0 || (P > 0 && (viewspace_grad == nullptr || radii == nullptr || max_radii2D == nullptr ||
-                                   xyz_gradient_accum == nullptr || denom == nullptr)))
-    return fail(DGS_E_ARG, "densify_stats: bad argument");
-  if (P == 0) return DGS_OK;
-  hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     viewspace_grad, radii, K, K_total, P, max_radii2D, xyz_gradient_accum, denom, skip_flag);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DGS_OK : fail_hip(e, "densify_stats");
 }
 
 int dgs_context_create(const DgsContextOptions* options, DgsContext** out) {

@@ -124,7 +124,48 @@ __device__ __forceinline__ float dgs_row_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ float dgs_sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
+
+// ---- deterministic totals over the blocks of a grid (blur loss: loss.hip, view loss: metrics.hip) ----------------
+// A block's two sums (fixed-order trees of non-negative terms) are added as 2^-24 fixed-point integers -- integer
+// addition is associative, so the result does not depend on the order in which the blocks arrive, unlike float atomics
+// -- and the last block to arrive converts them.  Words of the work area (zeroed by the launcher): [2..3] / [4..5] the
+// two 64-bit accumulators, [6] arrival counter, [7] sticky "not representable" flag; the words before and after belong
+// to the caller's results.  The fixed point covers totals below 2^40 ~ 1.1e12 at a resolution far below the rounding of
+// the block sums; a block sum that is NaN / Inf (a diverged render, a NaN in the ground truth) or a total that leaves the
+// range sets the flag, and the caller reports NaN, as float arithmetic would have.
+// Called by ONE thread per block with the block's sums (T: the type they were formed in, which is also the type of the
+// range test).  Returns true in the last block to arrive, with the two totals and the flag read back.
+constexpr double DGS_TOTALS_FX = 16777216.0;   // 2^24
+template <typename T>
+__device__ __forceinline__ bool dgs_totals_publish(T a, T c, float* __restrict__ work, unsigned long long& t0,
+                                                   unsigned long long& t1, bool& bad) {
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(work + 2);
+  unsigned int* flag = reinterpret_cast<unsigned int*>(work + 7);
+  const bool fin = __builtin_isfinite(a) && __builtin_isfinite(c) && a < (T)5.0e11 && c < (T)5.0e11;
+  if (!fin) {
+    atomicOr(flag, 1u);
+  } else {
+    const unsigned long long ia = (unsigned long long)__double2ll_rn((double)a * DGS_TOTALS_FX);
+    const unsigned long long ic = (unsigned long long)__double2ll_rn((double)c * DGS_TOTALS_FX);
+    const unsigned long long oa = atomicAdd(&acc[0], ia), oc = atomicAdd(&acc[1], ic);
+    if (oa + ia < oa || oc + ic < oc) atomicOr(flag, 1u);   // the 64-bit accumulator wrapped
+  }
+  __threadfence();
+  const unsigned int ticket = atomicAdd(reinterpret_cast<unsigned int*>(work + 6), 1u);
+  if (ticket != gridDim.x - 1) return false;
+  __threadfence();
+  t0 = atomicAdd(&acc[0], 0ull);
+  t1 = atomicAdd(&acc[1], 0ull);
+  bad = atomicOr(flag, 0u) != 0u;
+  return true;
+}
+
 // ---- host-side launch entry points (one per .hip file) -----------------------------------------------------
+// error reporting for every translation unit: set dgs_last_error's text (api.hip), return the code
+int dgs_fail_arg(const char* msg);
+int dgs_fail_hip(hipError_t e, const char* where);
+
 struct DgsView {  // per-launch scalars shared by the kernels
   int P, D, M, W, H, K;
   int gx, gy, T;  // tile grid and tiles per subframe
@@ -233,10 +274,6 @@ hipError_t dgs_launch_geometry_bwd(const DgsProblem& p, const DgsView& v, const 
 // (the contribution rows are those of the pose-only compositing instantiation: eight columns, the depth total in column 5)
 hipError_t dgs_launch_geometry_pose_bwd(const DgsProblem& p, const DgsView& v, const DgsCarve& c, const DgsBackwardIO& io,
                                         const float* contrib, float* sums, double* partials, hipStream_t s, int phases);
-hipError_t dgs_launch_blur_loss(const float* sub, const float* gt, int K, int C, int HW, float lambda_t,
-                                const float* lambda_dev, const float* scale, float* blur, float* dsub, float* losses,
-                                hipStream_t s);
-
 hipError_t dgs_launch_depth_sort(uint32_t* keys, uint32_t* keys_alt, uint32_t* order, uint32_t* order_alt, int K,
                                  uint32_t P, uint32_t* tmp, uint32_t* vis_dst, uint32_t* wide_flag, hipStream_t s,
                                  const uint32_t* cnt_src = nullptr, uint32_t* cnt_dst = nullptr,

@@ -218,9 +218,6 @@ KnnCarve carve_knn(int P, char* base) {
 
 }  // namespace
 
-extern int dgs_fail_arg(const char* msg);
-extern int dgs_fail_hip(hipError_t e, const char* where);
-
 extern "C" {
 
 size_t dgs_knn_tmp_bytes(int32_t P) { return carve_knn(P < 0 ? 0 : P, nullptr).total; }

@@ -12,12 +12,7 @@
 
 #include "dgs_common.h"
 
-extern int dgs_fail_arg(const char* msg);
-extern int dgs_fail_hip(hipError_t e, const char* where);
-
 namespace {
-
-__device__ __forceinline__ float sgnf(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
 
 // sum over the 256 threads of a block in a fixed order (lane order inside a wave, then wave order); valid in thread 0
 __device__ __forceinline__ double block_sum_256(double v, double* red) {
@@ -38,8 +33,8 @@ __device__ __forceinline__ double block_sum_256(double v, double* red) {
 // with torch's conventions: clamp and clamp_min pass the gradient on the bound, sign(0) = 0.  gamma:
 //   tone_map(x) = max((x - bound) / (1 - 2 bound), eps) ^ (1 / 2.2)   (losses.ToneMapping)
 // and its derivative as torch's pow backward forms it: (1 / 2.2) u ^ (1 / 2.2 - 1), exponents rounded to fp32.
-// work: 12 words, zeroed by the launcher -- [0] l1, [1] mse (fp32), [2..3] / [4..5] 2^-24 fixed-point accumulators of
-// the two block sums, [6] arrival counter, [7] "not representable" flag, [8..9] / [10..11] the two values as fp64.
+// work: 12 words, zeroed by the launcher -- [0] l1, [1] mse (fp32), [2..7] the deterministic totals' own words
+// (dgs_totals_publish, dgs_common.h), [8..9] / [10..11] the two values as fp64.
 template <int GAMMA>
 __global__ void __launch_bounds__(256)
 view_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt_base, const int32_t* __restrict__ gt_index,
@@ -64,37 +59,23 @@ view_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt_base,
       // d/dx of clamp_min(u, eps) ^ ex: zero below eps, (ex * uc ^ (ex - 1)) / (1 - 2 bound) from eps on
       dy = (u >= eps) ? (ex * powf(uc, ex1)) / inv_span : 0.0f;
     }
-    const float y = fminf(1.0f, fmaxf(0.0f, y0));
+    // (fmaxf / fminf drop a NaN operand, torch's clamp and clamp_min pass it on: a NaN in x must reach the totals)
+    const float y = (xv != xv) ? xv : fminf(1.0f, fmaxf(0.0f, y0));
     const bool pass = y0 >= 0.0f && y0 <= 1.0f;   // torch.clamp passes the gradient inside and on the bounds
     const float d = y - gt[e];
     l1 += (double)fabsf(d);
     l2 += (double)d * (double)d;
-    if (dL_dx != nullptr) dL_dx[e] = (pass && dy != 0.0f) ? (c_l1 * sgnf(d)) * dy : 0.0f;
+    if (dL_dx != nullptr) dL_dx[e] = (pass && dy != 0.0f) ? (c_l1 * dgs_sgn(d)) * dy : 0.0f;
   }
   if (work == nullptr) return;
   const double a = block_sum_256(l1, red), c = block_sum_256(l2, red);
   if (threadIdx.x != 0) return;
-  constexpr double FX = 16777216.0;   // 2^24
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(work + 2);
-  unsigned int* flag = reinterpret_cast<unsigned int*>(work + 7);
-  const bool fin = __builtin_isfinite(a) && __builtin_isfinite(c) && a < 5.0e11 && c < 5.0e11;
-  if (!fin) {
-    atomicOr(flag, 1u);
-  } else {
-    const unsigned long long ia = (unsigned long long)__double2ll_rn(a * FX);
-    const unsigned long long ic = (unsigned long long)__double2ll_rn(c * FX);
-    const unsigned long long oa = atomicAdd(&acc[0], ia), oc = atomicAdd(&acc[1], ic);
-    if (oa + ia < oa || oc + ic < oc) atomicOr(flag, 1u);
-  }
-  __threadfence();
-  const unsigned int ticket = atomicAdd(reinterpret_cast<unsigned int*>(work + 6), 1u);
-  if (ticket == gridDim.x - 1) {
-    __threadfence();
-    const unsigned long long t0 = atomicAdd(&acc[0], 0ull), t1 = atomicAdd(&acc[1], 0ull);
-    const bool bad = atomicOr(flag, 0u) != 0u;
+  unsigned long long t0, t1;
+  bool bad;
+  if (dgs_totals_publish(a, c, work, t0, t1, bad)) {
     const double nanv = __longlong_as_double(0x7ff8000000000000ll);
-    const double v1 = bad ? nanv : ((double)t0 / FX) / (double)E;
-    const double v2 = bad ? nanv : ((double)t1 / FX) / (double)E;
+    const double v1 = bad ? nanv : ((double)t0 / DGS_TOTALS_FX) / (double)E;
+    const double v2 = bad ? nanv : ((double)t1 / DGS_TOTALS_FX) / (double)E;
     work[0] = (float)v1;
     work[1] = (float)v2;
     reinterpret_cast<double*>(work + 8)[0] = v1;

@@ -226,9 +226,6 @@ rank_ordered_sum_kernel(const float* __restrict__ recv, uint64_t stride, float* 
 
 }  // namespace
 
-extern int dgs_fail_arg(const char* msg);
-extern int dgs_fail_hip(hipError_t e, const char* where);
-
 extern "C" {
 
 static void adam_scalars_of(const DgsAdamGroup& g, double beta1, double beta2, float* neg_step_size, float* bc2_sqrt) {

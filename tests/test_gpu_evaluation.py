@@ -304,6 +304,46 @@ def test_view_loss_kernel_against_torch_in_float64(gpu, kind, bound):
     assert np.count_nonzero(g) > 0.4 * E
 
 
+@pytest.mark.parametrize("H,W", [(7, 9), (20, 24), (300, 300)])
+def test_view_loss_totals_over_one_block_many_blocks_and_the_capped_grid(gpu, H, W):
+    """The totals of dgs_view_loss_grad (identity tone mapping) where the number of blocks changes who converts them:
+    E = 189 (one block), 1440 (six blocks: the last to arrive converts), 270000 (> 1024 * 256: capped grid, a second
+    trip of the stride loop).  The fp32 words are the rounding of the fp64 words, both agree with torch in float64
+    within 4 x the gap between torch's own fp32 and fp64 evaluation (the bar of the test above), and a NaN in x turns
+    all four values into NaN (torch's clamp passes a NaN on; the kernel's fminf / fmaxf clamp used to drop it and report
+    the loss of a zero pixel instead)."""
+    import torch
+    from deblurgs_amd import _lib
+    L = _lib.lib()
+    rng = np.random.default_rng(H * 1000 + W)
+    x = rng.uniform(-0.2, 1.3, (3, H, W)).astype(np.float32)
+    gt = rng.uniform(0.0, 1.0, (3, H, W)).astype(np.float32)
+    x.reshape(-1)[0:4] = [0.0, 1.0, -0.5, 2.0]                     # on the clamp bounds and far outside
+    gt.reshape(-1)[10:20] = np.clip(x.reshape(-1)[10:20], 0.0, 1.0)   # equal to gt
+    l1_64, mse_64, _ = view_loss_torch(x, gt, "identity", torch.float64, device="cuda")
+    l1_32, mse_32, _ = view_loss_torch(x, gt, "identity", torch.float32, device="cuda")
+    xs, gts = _t(x), _t(gt)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def totals():
+        work = torch.full((12,), 7.0, dtype=torch.float32, device="cuda")
+        _lib.check(L.dgs_view_loss_grad(xs.data_ptr(), gts.data_ptr(), None, 1, 3, H * W, _lib.TONE_IDENTITY, EPS32, 0.0,
+                                        None, None, work.data_ptr(), None, None, st), "dgs_view_loss_grad")
+        torch.cuda.synchronize()
+        return work[:2].cpu().numpy(), work[8:12].cpu().numpy().view(np.float64)
+
+    v32, v64 = totals()
+    for name, got, got32, w64, w32 in (("l1", v64[0], v32[0], float(l1_64), float(l1_32)),
+                                       ("mse", v64[1], v32[1], float(mse_64), float(mse_32))):
+        bar = 4.0 * abs(w32 - w64)
+        print(f"E {x.size} {name}: kernel {got!r} torch64 {w64!r} torch32 {w32!r} |diff| {abs(got - w64):.3e} bar {bar:.3e}")
+        assert got32 == np.float32(got)
+        assert abs(got - w64) <= bar, (name, got, w64, bar)
+    xs.view(-1)[x.size // 2] = float("nan")
+    v32, v64 = totals()
+    assert np.isnan(v32).all() and np.isnan(v64).all(), (v32, v64)
+
+
 # ------------------------------------------------------------------------------------------------ metrics
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_image_metrics_kernel_against_the_reference_fixture(gpu, name):

@@ -1018,6 +1018,83 @@ def test_slice_loss_kernel_equals_the_whole_view_loss(gpu, K, H, W, cuts):
     assert L.dgs_blur_loss_slice_grad(p(X), None, None, p(blur_c), p(gt), 33, 40, 3, H * W, 0.0, p(X), p(work), st) != 0
 
 
+@pytest.mark.parametrize("K,H,W,misalign", [(5, 6, 8, False), (16, 6, 8, False), (17, 6, 8, False), (32, 6, 8, False),
+                                            (33, 6, 8, False), (5, 7, 9, False), (5, 6, 8, True), (1, 6, 8, False),
+                                            (5, 20, 24, False), (3, 420, 420, False)])
+def test_blur_loss_dispatches_agree(gpu, K, H, W, misalign):
+    """Every kernel behind dgs_blur_loss_grad: the register-resident all-in-one kernels (K <= 16, K <= 32), the streaming
+    one (K = 33), the scalar path (E = 189, or a subframe pointer that is not 16-byte aligned), K = 1 (smoothness weight
+    and value exactly 0), two blocks (E = 1440: the arrival ticket decides who converts) and the capped grid
+    (E = 529200 > 512 * 256 * 4: a second trip of the stride loop).  Three calls per case -- forward only, all in one,
+    backward only (with the forward's blur handed in, and with blur = NULL) -- against torch autograd of the reference
+    expression in float64, and against each other BITWISE: the forward-only blur and loss words equal the all-in-one
+    call's, both backward-only gradients equal the all-in-one gradient.
+    FINDING about the kernels as they are: for 16 < K <= 32 on the 16-byte path the all-in-one kernel
+    (blur_loss_all_kernel<32, 2>) sums TWO elements per thread and the forward-only one (blur_loss_kernel<0, 4>) FOUR, so
+    the per-thread partial sums and the fp32 trees above them differ and the two loss words are equal only up to fp32
+    rounding (a float32 model of both summation orders at E = 144 disagrees in the last bit for 4 of 20 seeds at K = 17
+    and 9 of 20 at K = 32).  For those two cases the loss words are held to the float64 tolerance only; the blur and the
+    gradients, which are per element, stay bitwise.
+    Inputs: sub[1] == sub[0] on half the rows (sign(0) = 0 on both sides); gt is moved where it lies within 1e-4 of the
+    float64 blur, so that sign(blur - gt) -- discontinuous at 0 -- cannot be decided by the fp32 rounding of the blur
+    (K roundings of 2^-24 on values below 1: far below 1e-4)."""
+    import ctypes
+    import torch
+    from deblurgs_amd import _lib
+    L = _lib.lib()
+    torch.manual_seed(K * 1000 + H)
+    E = 3 * H * W
+    store = torch.rand(K * E + 1, device=gpu)
+    X = store[1:].view(K, 3, H, W) if misalign else store[:-1].view(K, 3, H, W)
+    assert (X.data_ptr() % 16 != 0) == misalign and X.is_contiguous()
+    if K > 1:
+        X[1, :, : H // 2] = X[0, :, : H // 2]
+    gt = torch.rand(3, H, W, device=gpu)
+    close = (X.double().mean(0) - gt.double()).abs() < 1e-4
+    gt[close] += 0.25
+    lam = 0.037
+    Xr = X.double().requires_grad_(True)
+    blur_ref = Xr.mean(0)
+    l1 = (blur_ref - gt.double()).abs().mean()
+    sm = (Xr[1:] - Xr[:-1]).abs().mean() if K > 1 else torch.zeros((), device=gpu, dtype=torch.float64)
+    (l1 + lam * sm).backward()
+    ref = Xr.grad
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    one = torch.ones(1, device=gpu)
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+
+    def call(blur, dsub, work):
+        _lib.check(L.dgs_blur_loss_grad(p(X), p(gt), K, 3, H * W, lam, p(one), p(blur), p(dsub), p(work), st),
+                   "dgs_blur_loss_grad")
+        torch.cuda.synchronize()
+
+    nan = float("nan")
+    blur_f, work_f = torch.full_like(gt, nan), torch.full((8,), nan, device=gpu)
+    call(blur_f, None, work_f)                                   # forward only
+    blur_a, work_a, d_a = torch.full_like(gt, nan), torch.full((8,), nan, device=gpu), torch.full((K, 3, H, W), nan, device=gpu)
+    call(blur_a, d_a, work_a)                                    # all in one
+    d_b, d_n = torch.full_like(d_a, nan), torch.full_like(d_a, nan)
+    call(blur_f, d_b, None)                                      # backward only, the forward's blur handed in
+    call(None, d_n, None)                                        # backward only, blur recomputed
+    gtol = 1e-9 + 1e-6 * float(ref.abs().max())
+    for name, blur, work in (("forward", blur_f, work_f), ("all-in-one", blur_a, work_a)):
+        eb = float((blur.double() - blur_ref.detach()).abs().max())
+        e0, e1 = abs(float(work[0]) - float(l1)), abs(float(work[1]) - float(sm))
+        print(f"K {K} E {E} misalign {misalign} {name}: blur err {eb:.3e} l1 err {e0:.3e} smooth err {e1:.3e}")
+        assert eb <= 1e-6 and e0 <= 1e-6 and e1 <= 1e-6, name
+    if K == 1:
+        assert float(work_f[1]) == 0.0 and float(work_a[1]) == 0.0
+    for name, d in (("all-in-one", d_a), ("backward, blur given", d_b), ("backward, blur = NULL", d_n)):
+        eg = float((d.double() - ref).abs().max())
+        print(f"K {K} E {E} misalign {misalign} {name}: gradient err {eg:.3e} bar {gtol:.3e}")
+        assert eg <= gtol, name
+    bits = lambda t: t.view(torch.int32)
+    assert torch.equal(bits(blur_f), bits(blur_a))
+    if not (16 < K <= 32 and E % 4 == 0 and not misalign):
+        assert torch.equal(bits(work_f[:2]), bits(work_a[:2]))
+    assert torch.equal(bits(d_b), bits(d_a)) and torch.equal(bits(d_n), bits(d_a))
+
+
 def test_densification_stats_match_reference_loop(gpu):
     """dgs_densify_stats against the reference's per-subframe Python loop (train.py:188-193,
     scene/gaussian_model.py:456-458) written with torch ops."""
