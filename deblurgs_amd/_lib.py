@@ -186,6 +186,18 @@ EXPORTS = {
     "dgs_testpose_backward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 6),
     "dgs_view_loss_grad": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 4 + [ctypes.c_float] * 2 +
                            [ctypes.c_void_p] * 6),
+    "dgs_adam_epoch_peek": (ctypes.c_int, [ctypes.POINTER(DgsAdamGroup), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)] +
+                            [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int32] + [ctypes.c_double] * 3 +
+                            [ctypes.c_void_p]),
+    "dgs_adam_epoch_step": (ctypes.c_int, [ctypes.POINTER(DgsAdamGroup)] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2 +
+                            [ctypes.c_int32] + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 2),
+    "dgs_testpose_forward_rows": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 5),
+    "dgs_testpose_backward_rows": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 6),
+    "dgs_view_loss_grad_rows": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 6 + [ctypes.c_float] * 2 +
+                                [ctypes.c_void_p] * 4),
+    "dgs_l2_ema_epoch": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
+                                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int32] +
+                         [ctypes.c_void_p] * 2),
     "dgs_image_metrics_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "dgs_image_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -9,6 +9,7 @@
 // Every total is deterministic: per-block sums in a fixed order, then either integer (fixed-point) atomics or a second
 // kernel that adds the blocks in index order.
 #include <math.h>
+#include <string.h>
 
 #include "dgs_common.h"
 
@@ -35,15 +36,12 @@ __device__ __forceinline__ double block_sum_256(double v, double* red) {
 // and its derivative as torch's pow backward forms it: (1 / 2.2) u ^ (1 / 2.2 - 1), exponents rounded to fp32.
 // work: 12 words, zeroed by the launcher -- [0] l1, [1] mse (fp32), [2..7] the deterministic totals' own words
 // (dgs_totals_publish, dgs_common.h), [8..9] / [10..11] the two values as fp64.
+// (the body of both kernels below: one image on the blocks of grid-x)
 template <int GAMMA>
-__global__ void __launch_bounds__(256)
-view_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt_base, const int32_t* __restrict__ gt_index,
-                 int n_gt, size_t E, float eps, float bound, const float* __restrict__ upstream, float* __restrict__ dL_dx,
-                 float* __restrict__ work, float* __restrict__ l2_ema, const uint32_t* __restrict__ skip_flag) {
-  __shared__ double red[256];
-  int gi = (gt_index != nullptr) ? gt_index[0] : 0;
-  if (gi < 0 || gi >= n_gt) gi = 0;   // (a corrupt index must not read out of bounds; testpose_kernel does the same)
-  const float* gt = gt_base + (size_t)gi * E;
+__device__ __forceinline__ void view_loss_image(const float* __restrict__ x, const float* __restrict__ gt, size_t E, float eps,
+                                                float bound, const float* __restrict__ upstream, float* __restrict__ dL_dx,
+                                                float* __restrict__ work, float* __restrict__ l2_ema,
+                                                const uint32_t* __restrict__ skip_flag, double* red) {
   const float up = (upstream != nullptr) ? upstream[0] : 1.0f;
   const float c_l1 = (float)((double)up / (double)E);
   const float inv_span = 1.0f - 2.0f * bound;
@@ -83,6 +81,65 @@ view_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt_base,
     // l2_error_ema = 0.6 l2_error_ema + 0.4 mse (test.py:178); a step whose forward overflowed its capacity does not count
     if (l2_ema != nullptr && (skip_flag == nullptr || skip_flag[0] == 0u)) l2_ema[0] = l2_ema[0] * 0.6f + (float)v2 * 0.4f;
   }
+}
+
+template <int GAMMA>
+__global__ void __launch_bounds__(256)
+view_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt_base, const int32_t* __restrict__ gt_index,
+                 int n_gt, size_t E, float eps, float bound, const float* __restrict__ upstream, float* __restrict__ dL_dx,
+                 float* __restrict__ work, float* __restrict__ l2_ema, const uint32_t* __restrict__ skip_flag) {
+  __shared__ double red[256];
+  int gi = (gt_index != nullptr) ? gt_index[0] : 0;
+  if (gi < 0 || gi >= n_gt) gi = 0;   // (a corrupt index must not read out of bounds; testpose_kernel does the same)
+  view_loss_image<GAMMA>(x, gt_base + (size_t)gi * E, E, eps, bound, upstream, dL_dx, work, l2_ema, skip_flag, red);
+}
+
+// G images in one launch (EpochPoseFit): image k = blockIdx.y of x [G,C,HW] against image row_begin + k of the stack, its
+// own gradient image and its own 12-word work area.  Grid-x is the single-image launcher's, so every image's block sums,
+// totals and gradient are those of a dgs_view_loss_grad call on it.
+template <int GAMMA>
+__global__ void __launch_bounds__(256)
+view_loss_rows_kernel(const float* __restrict__ x, const float* __restrict__ gt_base, int row_begin, size_t E, float eps,
+                      float bound, const float* __restrict__ upstream, float* __restrict__ dL_dx, float* __restrict__ work) {
+  __shared__ double red[256];
+  const size_t k = blockIdx.y;
+  view_loss_image<GAMMA>(x + k * E, gt_base + ((size_t)row_begin + k) * E, E, eps, bound, upstream,
+                         dL_dx != nullptr ? dL_dx + k * E : nullptr, work + 12 * k, nullptr, nullptr, red);
+}
+
+// l2_error_ema over an epoch (test.py:178): ema = 0.6 ema + 0.4 mse of the views IN THE ORDER OF THEIR TURNS.  work
+// [n,12]: the views' work areas by row; pos [n]: the turn of row r (the inverse of the epoch's order).  The rows of a
+// group whose forward overflowed (its skip word is non-zero) do not count.  One block: thread r files row r under its
+// turn, thread 0 walks the turns.
+struct EmaGroups {
+  const uint32_t* skip[DGS_MAX_K];
+  int32_t begin[DGS_MAX_K + 1];     // group g covers rows [begin[g], begin[g + 1])
+  int n_groups;
+};
+__global__ void __launch_bounds__(DGS_MAX_K)
+l2_ema_epoch_kernel(const float* __restrict__ work, const int32_t* __restrict__ pos, int n, EmaGroups groups,
+                    float* __restrict__ l2_ema) {
+  __shared__ int s_row[DGS_MAX_K];
+  __shared__ unsigned char s_skip[DGS_MAX_K];
+  const int r = threadIdx.x;
+  s_row[r] = -1;
+  __syncthreads();
+  if (r < n) {
+    int g = 0;
+    while (g < groups.n_groups - 1 && r >= groups.begin[g + 1]) g++;
+    s_skip[r] = (groups.skip[g] != nullptr && groups.skip[g][0] != 0u) ? 1 : 0;
+    const int turn = pos[r];
+    if (turn >= 0 && turn < n) s_row[turn] = r;   // (a corrupt position files nothing: no write out of bounds)
+  }
+  __syncthreads();
+  if (r != 0) return;
+  float ema = l2_ema[0];
+  for (int j = 0; j < n; j++) {
+    const int row = s_row[j];
+    if (row < 0 || s_skip[row]) continue;
+    ema = ema * 0.6f + work[12 * row + 1] * 0.4f;
+  }
+  l2_ema[0] = ema;
 }
 
 // ------------------------------------------------------------------------------------------- PSNR + SSIM
@@ -221,6 +278,57 @@ int dgs_view_loss_grad(const float* x, const float* gt, const int32_t* gt_index_
                        l2_ema, skip_flag);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "view_loss_grad");
+}
+
+int dgs_view_loss_grad_rows(const float* x, const float* gt, int32_t n_gt, int32_t row_begin, int32_t row_end, int32_t C,
+                            int32_t HW, int32_t tone_mapping, float eps, float bound, const float* upstream, float* dL_dx,
+                            float* work, dgs_stream_t stream) {
+  if (x == nullptr || gt == nullptr || work == nullptr || C < 1 || HW < 1)
+    return dgs_fail_arg("view_loss_grad_rows: null image, empty image or no work area");
+  if (n_gt < 1 || row_begin < 0 || row_end > n_gt || row_begin >= row_end)
+    return dgs_fail_arg("view_loss_grad_rows: n_gt < 1, empty row range or row_end > n_gt");
+  if (row_end - row_begin > DGS_MAX_K) return dgs_fail_arg("view_loss_grad_rows: more than DGS_MAX_K images");
+  if (tone_mapping != DGS_TONE_IDENTITY && tone_mapping != DGS_TONE_GAMMA)
+    return dgs_fail_arg("view_loss_grad_rows: tone_mapping must be DGS_TONE_IDENTITY or DGS_TONE_GAMMA");
+  if (tone_mapping == DGS_TONE_GAMMA && !(bound < 0.5f)) return dgs_fail_arg("view_loss_grad_rows: bound must be below 0.5");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int G = row_end - row_begin;
+  const size_t E = (size_t)C * (size_t)HW;
+  hipError_t e = dgs_launch_clear_words(reinterpret_cast<uint32_t*>(work), 12 * G, s);
+  if (e != hipSuccess) return dgs_fail_hip(e, "view_loss_grad_rows (clear)");
+  const size_t want = (E + 255) / 256;
+  const dim3 grid((uint32_t)(want < 1024 ? want : 1024), (uint32_t)G);   // grid-x: dgs_view_loss_grad's, a function of E only
+  if (tone_mapping == DGS_TONE_GAMMA)
+    hipLaunchKernelGGL(view_loss_rows_kernel<1>, grid, dim3(256), 0, s, x, gt, (int)row_begin, E, eps, bound, upstream, dL_dx, work);
+  else
+    hipLaunchKernelGGL(view_loss_rows_kernel<0>, grid, dim3(256), 0, s, x, gt, (int)row_begin, E, eps, bound, upstream, dL_dx, work);
+  e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "view_loss_grad_rows");
+}
+
+int dgs_l2_ema_epoch(const float* work, const int32_t* pos, int32_t n, const uint32_t* const* skip_flags,
+                     const int32_t* group_begin, int32_t n_groups, float* l2_ema, dgs_stream_t stream) {
+  if (work == nullptr || pos == nullptr || l2_ema == nullptr) return dgs_fail_arg("l2_ema_epoch: null pointer");
+  if (n < 1 || n > DGS_MAX_K) return dgs_fail_arg("l2_ema_epoch: n must be in 1..DGS_MAX_K");
+  if (n_groups < 0 || n_groups > n || (n_groups > 0 && (skip_flags == nullptr || group_begin == nullptr)))
+    return dgs_fail_arg("l2_ema_epoch: 0..n groups, with their skip words and row ranges");
+  EmaGroups g;
+  memset(&g, 0, sizeof(g));
+  g.n_groups = n_groups > 0 ? n_groups : 1;       // no groups: one group of all rows that is never skipped
+  g.begin[1] = n;
+  for (int i = 0; i < n_groups; i++) {
+    if (group_begin[i] < 0 || group_begin[i + 1] <= group_begin[i] || group_begin[i + 1] > n)
+      return dgs_fail_arg("l2_ema_epoch: group_begin must rise from 0 to n");
+    g.skip[i] = skip_flags[i];
+    g.begin[i] = group_begin[i];
+    g.begin[i + 1] = group_begin[i + 1];
+  }
+  if (n_groups > 0 && (group_begin[0] != 0 || group_begin[n_groups] != n))
+    return dgs_fail_arg("l2_ema_epoch: group_begin must rise from 0 to n");
+  hipLaunchKernelGGL(l2_ema_epoch_kernel, dim3(1), dim3(DGS_MAX_K), 0, reinterpret_cast<hipStream_t>(stream), work, pos,
+                     (int)n, g, l2_ema);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "l2_ema_epoch");
 }
 
 size_t dgs_image_metrics_tmp_bytes(int32_t W, int32_t H) {

@@ -6,6 +6,9 @@
 //     every survivor and the compaction of the six parameter tensors plus both Adam moments in three small launches
 //     and three scans, instead of ~100 boolean-mask / cat / index launches with optimiser-state surgery in Python.
 // Build with -ffp-contract=off: each statement rounds like the torch elementwise op it restates.
+#include <stdio.h>
+#include <string.h>
+
 #include "dgs_common.h"
 
 namespace {
@@ -31,7 +34,9 @@ struct AdamArgs {
 constexpr int ADAM_THREADS = 256;
 constexpr int ADAM_PER_BLOCK = ADAM_THREADS * 4;
 
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamArgs& a, float neg_step_size,
+// A: any struct with the update's constants (w1, w2, beta2, eps, clip): AdamArgs, EpochAdamArgs
+template <typename A>
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const A& a, float neg_step_size,
                                          float bc2_sqrt) {
   if (a.clip > 0.0f) g = fminf(a.clip, fmaxf(-a.clip, g));   // clip_grad_value_ (train.py:204-205)
   m = m + a.w1 * (g - m);                                     // exp_avg.lerp_(grad, 1 - beta1)
@@ -79,6 +84,59 @@ __global__ void __launch_bounds__(ADAM_THREADS) adam_kernel(AdamArgs a) {
       m[i] = mm;
       v[i] = vv;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------- Adam over an epoch
+// The test-view pose fit (deblurgs_amd/evaluation.py, EpochPoseFit): a dense Adam over [n, w] tensors whose row r gets
+// a non-zero gradient at ONE of an epoch's n_steps steps -- step pos[r] -- and zeros at all others.  Rows never interact
+// and Adam is elementwise, so all n_steps updates of an element are applied here by the thread that owns it: the
+// statements of adam_one, step after step, with that step's bias-corrected scalars and g = 0 at every step but pos[r].
+// PEEK = 1: only the pos[r] zero-gradient steps that precede the row's turn, the parameter written to peek_out (what
+// the row's view is rendered with), state untouched.  PEEK = 0: the whole epoch, parameter and both moments written.
+constexpr int EPOCH_ADAM_MAX_GROUPS = 4;
+struct EpochAdamArgs {
+  float* param[EPOCH_ADAM_MAX_GROUPS];
+  const float* grad[EPOCH_ADAM_MAX_GROUPS];
+  float* m[EPOCH_ADAM_MAX_GROUPS];
+  float* v[EPOCH_ADAM_MAX_GROUPS];
+  float* peek_out[EPOCH_ADAM_MAX_GROUPS];
+  int width[EPOCH_ADAM_MAX_GROUPS];      // w: elements per row
+  int elem_end[EPOCH_ADAM_MAX_GROUPS];   // inclusive prefix of (row_end - row_begin) * w per group
+  int n_groups, row_begin, row_end, n_steps;
+  const int32_t* pos;                    // [n]: the step of row r's turn; outside [0, n_steps) counts as 0
+  const float* scalars;                  // [n_steps, 2 n_groups]: (neg_step_size, bc2_sqrt) of group i at [j][2 i]
+  float beta2, w1, w2, eps, clip;
+  const uint32_t* skip;
+};
+
+template <int PEEK>
+__global__ void __launch_bounds__(64) adam_epoch_kernel(EpochAdamArgs a) {
+  if (!PEEK && a.skip != nullptr && a.skip[0] != 0u) return;   // the epoch's gradients come from a truncated forward
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  int gi = 0;
+#pragma unroll
+  for (int i = 0; i < EPOCH_ADAM_MAX_GROUPS - 1; i++)
+    if (i < a.n_groups - 1 && t >= a.elem_end[i]) gi = i + 1;
+  if (t >= a.elem_end[a.n_groups - 1]) return;
+  const int e = t - (gi == 0 ? 0 : a.elem_end[gi - 1]);
+  const int w = a.width[gi];
+  const int row = a.row_begin + e / w;
+  const size_t at = (size_t)row * w + (e % w);
+  int turn = a.pos[row];
+  if (turn < 0 || turn >= a.n_steps) turn = 0;
+  float p = a.param[gi][at], m = a.m[gi][at], v = a.v[gi][at];
+  const float g_turn = PEEK ? 0.0f : a.grad[gi][at];
+  const int last = PEEK ? turn : a.n_steps;
+  const float* sc = a.scalars + 2 * gi;
+  for (int j = 0; j < last; j++)
+    adam_one(p, j == turn ? g_turn : 0.0f, m, v, a, sc[(size_t)j * 2 * a.n_groups], sc[(size_t)j * 2 * a.n_groups + 1]);
+  if (PEEK) {
+    a.peek_out[gi][at] = p;
+  } else {
+    a.param[gi][at] = p;
+    a.m[gi][at] = m;
+    a.v[gi][at] = v;
   }
 }
 
@@ -297,6 +355,63 @@ int dgs_adam_scalars(const DgsAdamGroup* groups, int32_t n_groups, double beta1,
     adam_scalars_of(groups[i], beta1, beta2, &out[2 * i], &out[2 * i + 1]);
   }
   return DGS_OK;
+}
+
+static int adam_epoch_impl(const char* who, bool peek, const DgsAdamGroup* groups, int32_t n_groups, float* const* peek_out,
+                           int32_t n, int32_t row_begin, int32_t row_end, const int32_t* pos, const float* scalars,
+                           int32_t n_steps, double beta1, double beta2, double eps, const uint32_t* skip_flag,
+                           dgs_stream_t stream) {
+  char msg[160];
+#define DGS_EPOCH_FAIL(text) return (snprintf(msg, sizeof(msg), "%s: %s", who, text), dgs_fail_arg(msg))
+  if (groups == nullptr || n_groups < 1 || n_groups > EPOCH_ADAM_MAX_GROUPS) DGS_EPOCH_FAIL("1..4 groups");
+  if (n < 1 || n > (1 << 20)) DGS_EPOCH_FAIL("n must be in 1..2^20");
+  if (row_begin < 0 || row_end > n || row_begin >= row_end) DGS_EPOCH_FAIL("empty row range or row_end > n");
+  if (n_steps < 1 || n_steps > DGS_MAX_K) DGS_EPOCH_FAIL("n_steps must be in 1..DGS_MAX_K");
+  if (pos == nullptr || scalars == nullptr) DGS_EPOCH_FAIL("pos or scalars is null");
+  if (peek && peek_out == nullptr) DGS_EPOCH_FAIL("peek_out is null");
+  EpochAdamArgs a;
+  memset(&a, 0, sizeof(a));
+  int total = 0;
+  for (int i = 0; i < n_groups; i++) {
+    const DgsAdamGroup& g = groups[i];
+    if (g.param == nullptr || g.exp_avg == nullptr || g.exp_avg_sq == nullptr) DGS_EPOCH_FAIL("null state pointer");
+    if (peek ? peek_out[i] == nullptr : g.grad == nullptr) DGS_EPOCH_FAIL(peek ? "null peek_out tensor" : "null gradient");
+    if (g.numel == 0 || g.numel % (uint64_t)n != 0 || g.numel / (uint64_t)n > 64) DGS_EPOCH_FAIL("numel must be n x (1..64)");
+    a.param[i] = g.param; a.grad[i] = g.grad; a.m[i] = g.exp_avg; a.v[i] = g.exp_avg_sq;
+    a.peek_out[i] = peek ? peek_out[i] : nullptr;
+    a.width[i] = (int)(g.numel / (uint64_t)n);
+    total += (row_end - row_begin) * a.width[i];
+    a.elem_end[i] = total;
+  }
+#undef DGS_EPOCH_FAIL
+  a.n_groups = n_groups; a.row_begin = row_begin; a.row_end = row_end; a.n_steps = n_steps;
+  a.pos = pos; a.scalars = scalars;
+  a.beta2 = (float)beta2;
+  a.w1 = (float)(1.0 - beta1);
+  a.w2 = (float)(1.0 - beta2);
+  a.eps = (float)eps;
+  a.clip = 0.0f;
+  a.skip = skip_flag;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (peek)
+    hipLaunchKernelGGL(adam_epoch_kernel<1>, dim3((total + 63) / 64), dim3(64), 0, s, a);
+  else
+    hipLaunchKernelGGL(adam_epoch_kernel<0>, dim3((total + 63) / 64), dim3(64), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, who);
+}
+
+int dgs_adam_epoch_peek(const DgsAdamGroup* groups, int32_t n_groups, float* const* peek_out, int32_t n, int32_t row_begin,
+                        int32_t row_end, const int32_t* pos, const float* scalars, int32_t n_steps, double beta1,
+                        double beta2, double eps, dgs_stream_t stream) {
+  return adam_epoch_impl("adam_epoch_peek", true, groups, n_groups, peek_out, n, row_begin, row_end, pos, scalars, n_steps,
+                         beta1, beta2, eps, nullptr, stream);
+}
+int dgs_adam_epoch_step(const DgsAdamGroup* groups, int32_t n_groups, int32_t n, int32_t row_begin, int32_t row_end,
+                        const int32_t* pos, const float* scalars, int32_t n_steps, double beta1, double beta2, double eps,
+                        const uint32_t* skip_flag, dgs_stream_t stream) {
+  return adam_epoch_impl("adam_epoch_step", false, groups, n_groups, nullptr, n, row_begin, row_end, pos, scalars, n_steps,
+                         beta1, beta2, eps, skip_flag, stream);
 }
 
 int dgs_rank_ordered_sum(const float* recv, uint64_t stride, float* own, uint64_t n, int32_t world, int32_t rank,

@@ -385,6 +385,78 @@ __global__ void testpose_kernel(const float* __restrict__ rot, const float* __re
   }
 }
 
+// The same chain for the views [row_begin, row_end) of an epoch at once (EpochPoseFit): slot k = row - row_begin of the
+// [G,4,4] / [G,4,4] / [G,3] camera tensors.  MODE 0: one thread per view.  MODE 1: seven threads per view (four
+// quaternion components, three translation components); only the rows of the range are written.
+// The statements are testpose_kernel's, RESTATED rather than shared: every row's results must be that kernel's bit for
+// bit, and with one inlined body for both, the compiler packs and fuses other multiply-adds of the float product
+// view @ proj than it does in testpose_kernel as it stands (29 -> 30 v_pk_fma_f32), which would change the existing
+// kernel's full_proj.
+template <int MODE>
+__global__ void testpose_rows_kernel(const float* __restrict__ rot, const float* __restrict__ trans, int row_begin, int G,
+                                     const float* __restrict__ proj, float* __restrict__ view, float* __restrict__ full,
+                                     float* __restrict__ campos, const float* __restrict__ dL_dview,
+                                     const float* __restrict__ dL_dfull, float* __restrict__ dL_drot,
+                                     float* __restrict__ dL_dtrans) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (MODE == 0) {
+    if (t >= G) return;
+    const int idx = row_begin + t;
+    view += 16 * t;
+    full += 16 * t;
+    campos += 3 * t;
+    D6 q[4], R[9];
+    for (int i = 0; i < 4; i++) q[i] = cst((double)(rot[4 * idx + i] + 1e-8f));
+    quat_rot(q, R);
+    float wv[16];
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) wv[4 * r + c] = (float)R[3 * r + c].v;
+      wv[4 * r + 3] = 0.0f;
+    }
+    for (int c = 0; c < 3; c++) wv[12 + c] = trans[3 * idx + c];
+    wv[15] = 1.0f;
+    for (int i = 0; i < 16; i++) view[i] = wv[i];
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) {
+        float acc = 0.0f;
+        for (int j = 0; j < 4; j++) acc += wv[4 * r + j] * proj[4 * j + c];
+        full[4 * r + c] = acc;
+      }
+    for (int d = 0; d < 3; d++)
+      campos[d] = (float)(-((double)wv[12] * R[3 * d].v + (double)wv[13] * R[3 * d + 1].v + (double)wv[14] * R[3 * d + 2].v));
+  } else {
+    if (t >= 7 * G) return;
+    const int k = t / 7, c7 = t - 7 * k;
+    const int idx = row_begin + k;
+    const bool is_rot = c7 < 4;
+    const int comp = is_rot ? c7 : c7 - 4;
+    dL_dview += 16 * k;
+    dL_dfull += 16 * k;
+    float g;
+    if (is_rot) {
+      D6 q[4], R[9];
+      for (int i = 0; i < 4; i++) q[i] = var((double)(rot[4 * idx + i] + 1e-8f), i == comp);
+      quat_rot(q, R);
+      double acc = 0.0;
+      for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+          double G_ = (double)dL_dview[4 * r + c];
+          for (int j = 0; j < 4; j++) G_ += (double)dL_dfull[4 * r + j] * (double)proj[4 * c + j];
+          acc += G_ * R[3 * r + c].d[0];
+        }
+      g = (float)acc;
+    } else {
+      double G_ = (double)dL_dview[12 + comp];
+      for (int j = 0; j < 4; j++) G_ += (double)dL_dfull[12 + j] * (double)proj[4 * comp + j];
+      g = (float)G_;
+    }
+    if (is_rot)
+      dL_drot[4 * idx + comp] = g;
+    else
+      dL_dtrans[3 * idx + comp] = g;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,6 +537,36 @@ int dgs_testpose_backward(const float* rot, const float* trans, const int32_t* i
   hipLaunchKernelGGL(testpose_kernel<1>, dim3((7 * n + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), rot,
                      trans, idx_dev, idx, n, proj, nullptr, nullptr, nullptr, dL_dview, dL_dfull, dL_drot, dL_dtrans);
   return hipGetLastError() == hipSuccess ? DGS_OK : DGS_E_HIP;
+}
+
+int dgs_testpose_forward_rows(const float* rot, const float* trans, int32_t n, int32_t row_begin, int32_t row_end,
+                              const float* proj, float* view, float* full, float* campos, dgs_stream_t stream) {
+  if (rot == nullptr || trans == nullptr || proj == nullptr || view == nullptr || full == nullptr || campos == nullptr)
+    return dgs_fail_arg("testpose_forward_rows: null pointer");
+  if (n < 1 || n > (1 << 24) || row_begin < 0 || row_end > n || row_begin >= row_end)
+    return dgs_fail_arg("testpose_forward_rows: n < 1, empty row range or row_end > n");
+  if (row_end - row_begin > DGS_MAX_K) return dgs_fail_arg("testpose_forward_rows: more than DGS_MAX_K rows");
+  const int G = row_end - row_begin;
+  hipLaunchKernelGGL(testpose_rows_kernel<0>, dim3((G + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), rot,
+                     trans, (int)row_begin, G, proj, view, full, campos, nullptr, nullptr, nullptr, nullptr);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "testpose_forward_rows");
+}
+
+int dgs_testpose_backward_rows(const float* rot, const float* trans, int32_t n, int32_t row_begin, int32_t row_end,
+                               const float* proj, const float* dL_dview, const float* dL_dfull, float* dL_drot,
+                               float* dL_dtrans, dgs_stream_t stream) {
+  if (rot == nullptr || trans == nullptr || proj == nullptr || dL_dview == nullptr || dL_dfull == nullptr ||
+      dL_drot == nullptr || dL_dtrans == nullptr)
+    return dgs_fail_arg("testpose_backward_rows: null pointer");
+  if (n < 1 || n > (1 << 24) || row_begin < 0 || row_end > n || row_begin >= row_end)
+    return dgs_fail_arg("testpose_backward_rows: n < 1, empty row range or row_end > n");
+  if (row_end - row_begin > DGS_MAX_K) return dgs_fail_arg("testpose_backward_rows: more than DGS_MAX_K rows");
+  const int G = row_end - row_begin;
+  hipLaunchKernelGGL(testpose_rows_kernel<1>, dim3((7 * G + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     rot, trans, (int)row_begin, G, proj, nullptr, nullptr, nullptr, dL_dview, dL_dfull, dL_drot, dL_dtrans);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "testpose_backward_rows");
 }
 
 }  // extern "C"

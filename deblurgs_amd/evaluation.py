@@ -24,6 +24,25 @@ Semantics are the reference's: Adam (rates 5e-5 / 5e-4, eps 1e-15) runs over the
 (rows with zero gradient still move by their momentum, as torch's dense Adam moves them), StepLR(num_iter // 20, 0.9)
 advances once per epoch, an epoch visits every view once in shuffled order.
 
+`EpochPoseFit` (opt-in: optimize_test_pose(mode="epoch")) runs the same fit with ONE launch chain per epoch instead of one
+per view: all n views of an epoch go through one K = n rasteriser call (or one call per group of `views_per_call` rows).
+No update changes.  Adam is elementwise, row i of `_rot` / `_trans` gets a non-zero gradient only at view i's turn, and
+that gradient depends on row i alone; so within an epoch with order o, row i at position p_i sees p_i zero-gradient
+steps (it still moves by its momentum), one real step at the parameters it has THEN, and n - 1 - p_i more zero-gradient
+steps, each with that global step's bias corrections -- and rows never interact.  The chain of a group of rows is
+
+    parameters of every row at ITS turn (p_i zero-gradient steps)   dgs_adam_epoch_peek
+    -> the G cameras                                                dgs_testpose_forward_rows
+    K = G rasterisation                                             dgs_forward            (capacity sized ahead)
+    the G losses and dL/drender                                     dgs_view_loss_grad_rows
+    dL/d{world_view, full_proj} [G,4,4]                             dgs_backward_pose_only
+    -> rows of dL/dquaternion, dL/dtranslation                      dgs_testpose_backward_rows
+    the epoch's n Adam steps of those rows                          dgs_adam_epoch_step
+    (after the last group) l2_error_ema in the order of the turns   dgs_l2_ema_epoch
+
+One difference from the sequential fit: there a forward that overflows its capacity skips ONE step; here it skips the whole
+epoch of its group's rows (all n steps of those rows, zero-gradient ones included) -- dropped() counts the view-steps.
+
 LPIPS is not computed (its network weights are not part of this package); `evaluate` returns (psnr, ssim).
 `initialize_test_pose` (COLMAP registration of unposed test images) and the dataset readers are out of scope.
 """
@@ -160,6 +179,52 @@ def step_lrs(epochs, num_iter_per_view):
     return out
 
 
+def _capacity_for(need):
+    """The capacity for poses that need `need` duplicates at the start: half as much again + 16384, rounded up to 1/32 of
+    its leading power of two (at least 1024)."""
+    cap = need + need // 2 + 16384
+    q = 1 << max(cap.bit_length() - 5, 10)
+    return -(-cap // q) * q
+
+
+def step_rows(steps_done, orders, first_epoch, num_iter_per_view):
+    """The sequential fit's schedule on the host (no device is touched): one HYPER_WORDS row per step -- [0] the view
+    index (int32), [1:5] dgs_adam_scalars' (-(lr / (1 - beta1^t)), sqrt(1 - beta2^t)) for rot and trans at the step's count
+    t = steps_done + 1, ... and its epoch's learning rates.  orders: one view order per epoch; first_epoch: the StepLR
+    epoch the first of them is."""
+    L = _lib.lib()
+    lrs = step_lrs(first_epoch + len(orders), num_iter_per_view)[first_epoch:]
+    rows = np.zeros((sum(len(o) for o in orders), FusedPoseFit.HYPER_WORDS), dtype=np.float32)
+    groups = (_lib.DgsAdamGroup * 2)()
+    tmp = (ctypes.c_float * 4)()
+    t, i = int(steps_done), 0
+    for order, (lr_rot, lr_trans) in zip(orders, lrs):
+        for idx in order:
+            t += 1
+            groups[0].lr, groups[0].step = lr_rot, t
+            groups[1].lr, groups[1].step = lr_trans, t
+            _lib.check(L.dgs_adam_scalars(groups, 2, 0.9, 0.999, tmp), "dgs_adam_scalars")
+            rows[i, :1].view(np.int32)[0] = int(idx)
+            rows[i, 1:5] = np.frombuffer(tmp, dtype=np.float32)
+            i += 1
+    return rows
+
+
+def epoch_rows(steps_done, orders, first_epoch, num_iter_per_view):
+    """The epoch-fused fit's schedule on the host: one row of 5 n words per epoch -- [0:n] pos (int32), pos[order[j]] = j,
+    the turn of every view; [n:5n] the [n,4] scalars of the epoch's n steps, words [1:5] of step_rows' rows e n + j."""
+    n = len(orders[0]) if len(orders) else 0
+    if any(sorted(o) != list(range(n)) for o in orders):
+        raise ValueError("every epoch's order must be a permutation of the views")
+    per_step = step_rows(steps_done, orders, first_epoch, num_iter_per_view).reshape(len(orders), n, FusedPoseFit.HYPER_WORDS)
+    rows = np.zeros((len(orders), 5 * n), dtype=np.float32)
+    pos = rows[:, :n].view(np.int32)
+    for e, order in enumerate(orders):
+        pos[e, np.asarray(order, dtype=np.int64)] = np.arange(n, dtype=np.int32)
+    rows[:, n:] = per_step[:, :, 1:5].reshape(len(orders), 4 * n)
+    return rows
+
+
 class FusedPoseFit:
     HYPER_WORDS = 8      # [0] view index (int32), [1:5] Adam's (-(lr / (1 - beta1^t)), sqrt(1 - beta2^t)) for rot, trans
 
@@ -256,9 +321,7 @@ class FusedPoseFit:
             out = raster_call.forward_out(self.color, None, self.radii, self._host)
             R, _ = raster_call.forward(dev, prob, out, self._host, None)
             need = max(need, int(R))
-        cap = need + need // 2 + 16384
-        q = 1 << max(cap.bit_length() - 5, 10)
-        return -(-cap // q) * q
+        return _capacity_for(need)
 
     def _structs(self):
         m = self.model
@@ -324,20 +387,7 @@ class FusedPoseFit:
         """Uploads the device schedule of a run -- one 8-word row per step: the view index and Adam's scalars for the
         step's count and its epoch's learning rates -- and returns the number of steps.  orders: one view order per
         epoch (epoch_orders); first_epoch: the StepLR epoch the first of them is."""
-        L = _lib.lib()
-        lrs = step_lrs(first_epoch + len(orders), self.num_iter_per_view)[first_epoch:]
-        rows = np.zeros((sum(len(o) for o in orders), self.HYPER_WORDS), dtype=np.float32)
-        t, i = self.steps, 0
-        tmp = (ctypes.c_float * 4)()
-        for order, (lr_rot, lr_trans) in zip(orders, lrs):
-            for idx in order:
-                t += 1
-                self._groups[0].lr, self._groups[0].step = lr_rot, t
-                self._groups[1].lr, self._groups[1].step = lr_trans, t
-                _lib.check(L.dgs_adam_scalars(self._groups, 2, 0.9, 0.999, tmp), "dgs_adam_scalars")
-                rows[i, :1].view(np.int32)[0] = int(idx)
-                rows[i, 1:5] = np.frombuffer(tmp, dtype=np.float32)
-                i += 1
+        rows = step_rows(self.steps, orders, first_epoch, self.num_iter_per_view)
         self._sched = torch.from_numpy(rows).to(self.hyper.device)
         self._sched_pos = 0
         if self._graph is None:
@@ -375,12 +425,243 @@ class FusedPoseFit:
             return [self.model(i) for i in range(self.n)]
 
 
+class _EpochGroup:
+    """The buffers, structs and captured graph of one group of rows [begin, end) of an EpochPoseFit."""
+
+    def __init__(self, begin, end):
+        self.begin, self.end, self.G = begin, end, end - begin
+        self.graph = None
+
+
+class EpochPoseFit:
+    """The fit of FusedPoseFit with one launch chain per epoch and group of rows (module docstring): the same updates,
+    n times fewer chains.  views_per_call: None = all n views in one K = n call; a number caps the views per call (memory:
+    every call holds its own K = G images and lists) -- consecutive row groups of that size, each its own chain, buffers
+    and captured graph, replayed one after the other.  n <= DGS_MAX_K views (an epoch's schedule is one device block)."""
+    ROW_WORDS = 5         # per view and epoch: pos, then Adam's four scalars of one step
+
+    def __init__(self, cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, model=None, tile_cull=None,
+                 capacity=None, views_per_call=None):
+        """As FusedPoseFit.  capacity: duplicates EVERY group's lists are sized for (None: per group, 1.5 x the count of one
+        exact K = G forward at the start poses + 16384, rounded up as FusedPoseFit rounds)."""
+        if not getattr(cloud, "fused_activations", False):
+            raise NotImplementedError("EpochPoseFit needs a cloud with fused_activations")
+        self.cloud = cloud
+        dev = cloud._xyz.device
+        if dev.type != "cuda":
+            raise RuntimeError("EpochPoseFit needs a cloud on a HIP device (no CPU fallback)")
+        self.model = model if model is not None else TestPoseModel(cams, device=dev)
+        m = self.model
+        self.n = n = len(m)
+        if n > _lib.DGS_MAX_K:
+            raise NotImplementedError(f"EpochPoseFit fits at most DGS_MAX_K = {_lib.DGS_MAX_K} views (got {n}): an epoch's "
+                                      "schedule is one device block; use the sequential fit")
+        c0 = m.cams[0]
+        for c in m.cams:
+            if (c.image_width, c.image_height, c.FoVx, c.FoVy, c.znear, c.zfar) != \
+                    (c0.image_width, c0.image_height, c0.FoVx, c0.FoVy, c0.znear, c0.zfar):
+                raise NotImplementedError("EpochPoseFit renders the views of an epoch in one call: they must share image "
+                                          "size and intrinsics")
+        per_call = n if views_per_call is None else int(views_per_call)
+        if per_call < 1:
+            raise ValueError("views_per_call must be at least 1")
+        per_call = min(per_call, n)
+        self.H, self.W = H, W = int(c0.image_height), int(c0.image_width)
+        self.num_iter_per_view = int(num_iter_per_view)
+        self.tone_mapping, self._tone, self._eps, self._bound = _tone_args(tone_mapping)
+        f32 = dict(dtype=torch.float32, device=dev)
+        gt = torch.stack(list(gt_images)) if not torch.is_tensor(gt_images) else gt_images
+        self.gt = gt.to(**f32).contiguous()
+        if tuple(self.gt.shape) != (n, 3, H, W):
+            raise ValueError(f"gt_images must be [{n},3,{H},{W}]")
+        self.bg = bg.to(**f32).contiguous()
+        self.proj = m.projection_matrix(0).to(**f32).contiguous()
+        self.cull = dgr.TILE_CULL if tile_cull is None else bool(tile_cull)
+        self.steps = 0                # Adam steps enqueued so far: epochs x n
+        self._sched = None
+        P = cloud._xyz.shape[0]
+        L = _lib.lib()
+        # ---- what all groups share (each writes its own rows): the epoch's device block, the turn-time parameters, the
+        # gradients, the work areas, Adam's moments
+        self.block = torch.zeros(self.ROW_WORDS * n, **f32)      # [0:n] pos (int32), [n:5n] the [n,4] scalars
+        self._zero_block = torch.zeros_like(self.block)
+        self.peek = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
+        self.g_rot, self.g_trans = torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)
+        self.work = torch.zeros((n, 12), **f32)      # dgs_view_loss_grad_rows' work areas by row: [r,0] l1, [r,1] mse
+        self.l2_ema = torch.zeros(1, **f32)
+        self.exp_avg = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
+        self.exp_avg_sq = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
+        self._adam = (_lib.DgsAdamGroup * 2)(
+            _lib.DgsAdamGroup(m._rot.data_ptr(), self.g_rot.data_ptr(), self.exp_avg[0].data_ptr(),
+                              self.exp_avg_sq[0].data_ptr(), m._rot.numel(), ROT_LR, 1),
+            _lib.DgsAdamGroup(m._trans.data_ptr(), self.g_trans.data_ptr(), self.exp_avg[1].data_ptr(),
+                              self.exp_avg_sq[1].data_ptr(), m._trans.numel(), TRANS_LR, 1))
+        self._peek_out = (ctypes.c_void_p * 2)(self.peek[0].data_ptr(), self.peek[1].data_ptr())
+        # ---- per group: the cameras, images, lists and gradient matrices of its K = G call
+        self.groups = [_EpochGroup(b, min(b + per_call, n)) for b in range(0, n, per_call)]
+        for g in self.groups:
+            G = g.G
+            g.view, g.full, g.campos = torch.empty((G, 4, 4), **f32), torch.empty((G, 4, 4), **f32), torch.empty((G, 3), **f32)
+            g.color, g.dcolor = torch.empty((G, 3, H, W), **f32), torch.empty((G, 3, H, W), **f32)
+            g.radii = torch.empty((G, P), dtype=torch.int32, device=dev)
+            g.drops = torch.zeros(1, dtype=torch.int32, device=dev)
+            g.g_view, g.g_proj = torch.empty((G, 4, 4), **f32), torch.empty((G, 4, 4), **f32)
+            g.host = torch.zeros(8, dtype=torch.int32).pin_memory()
+            g.geom = torch.empty(L.dgs_geom_state_bytes(P, G), dtype=torch.uint8, device=dev)
+            g.image = torch.empty(L.dgs_image_state_bytes(W, H, G), dtype=torch.uint8, device=dev)
+            g.capacity = int(capacity) if capacity is not None else self._learn_capacity(g)
+            g.binning = torch.empty(L.dgs_binning_state_bytes(g.capacity, W, H, G), dtype=torch.uint8, device=dev)
+            g.scratch = torch.empty(L.dgs_backward_scratch_bytes(g.capacity, P, G), dtype=torch.uint8, device=dev)
+            g.skip_ptr = g.geom.data_ptr() + raster_call.skip_word_offset(P, W, H, G)
+            g.prob = self._problem(g, g.binning)
+            g.out = raster_call.forward_out(g.color, None, g.radii, g.host, drop_counter=g.drops)
+            g.out_probe = raster_call.forward_out(g.color, None, g.radii, g.host)    # gradients(): skips nothing, counts nothing
+            g.io = _lib.DgsBackwardIO()
+            g.io.num_rendered = g.capacity
+            g.io.radii, g.io.dL_dout_color = _ptr(g.radii), _ptr(g.dcolor)
+            g.io.scratch, g.io.scratch_bytes = _ptr(g.scratch), g.scratch.numel()
+            g.io.dL_dviewmatrix, g.io.dL_dprojmatrix = _ptr(g.g_view), _ptr(g.g_proj)
+        self.capacity = max(g.capacity for g in self.groups)
+        self._skips = (ctypes.c_void_p * len(self.groups))(*[g.skip_ptr for g in self.groups])
+        self._begins = (ctypes.c_int32 * (len(self.groups) + 1))(*([g.begin for g in self.groups] + [n]))
+
+    # ------------------------------------------------------------------------------------------------ plumbing
+    def _problem(self, g, binning=None):
+        cloud, c0 = self.cloud, self.model.cams[0]
+        settings = dgr.GaussianRasterizationSettings(
+            image_height=self.H, image_width=self.W, tanfovx=math.tan(c0.FoVx * 0.5), tanfovy=math.tan(c0.FoVy * 0.5),
+            bg=self.bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
+            sh_degree=cloud.active_sh_degree, campos=g.campos, prefiltered=False, debug=False)
+        rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
+        raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
+        return raster_call.problem(g.G, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
+                                   None, g.view, g.full, g.campos, settings, self.bg, self.cull, 0, raw=raw,
+                                   geom=g.geom, image=g.image, binning=binning)
+
+    def _pose_forward(self, g, rot, trans, stream):
+        _lib.check(_lib.lib().dgs_testpose_forward_rows(_ptr(rot), _ptr(trans), self.n, g.begin, g.end, _ptr(self.proj),
+                                                        _ptr(g.view), _ptr(g.full), _ptr(g.campos), stream),
+                   "dgs_testpose_forward_rows")
+
+    @torch.no_grad()
+    def _learn_capacity(self, g):
+        """One exact (two-phase) K = G forward of the group at its start poses."""
+        dev = self.cloud._xyz.device
+        self._pose_forward(g, self.model._rot, self.model._trans, _stream(dev))
+        out = raster_call.forward_out(g.color, None, g.radii, g.host)
+        R, _ = raster_call.forward(dev, self._problem(g), out, g.host, None)
+        return _capacity_for(int(R))
+
+    @torch.no_grad()
+    def _enqueue(self, g, apply=True):
+        """The launches of one group's epoch on the current stream, the schedule read from the device block."""
+        L = _lib.lib()
+        n = self.n
+        stream = _stream(self.cloud._xyz.device)
+        pos = ctypes.c_void_p(self.block.data_ptr())
+        scalars = ctypes.c_void_p(self.block.data_ptr() + 4 * n)
+        skip = ctypes.c_void_p(g.skip_ptr)
+        _lib.check(L.dgs_adam_epoch_peek(self._adam, 2, self._peek_out, n, g.begin, g.end, pos, scalars, n, 0.9, 0.999,
+                                         ADAM_EPS, stream), "dgs_adam_epoch_peek")
+        self._pose_forward(g, self.peek[0], self.peek[1], stream)
+        _lib.check(L.dgs_forward(ctypes.byref(g.prob), ctypes.byref(g.out if apply else g.out_probe), g.capacity, stream),
+                   "dgs_forward")
+        _lib.check(L.dgs_view_loss_grad_rows(_ptr(g.color), _ptr(self.gt), n, g.begin, g.end, 3, self.H * self.W, self._tone,
+                                             self._eps, self._bound, None, _ptr(g.dcolor), _ptr(self.work, 12 * g.begin),
+                                             stream), "dgs_view_loss_grad_rows")
+        _lib.check(L.dgs_backward_pose_only(ctypes.byref(g.prob), ctypes.byref(g.io), stream), "dgs_backward_pose_only")
+        _lib.check(L.dgs_testpose_backward_rows(_ptr(self.peek[0]), _ptr(self.peek[1]), n, g.begin, g.end, _ptr(self.proj),
+                                                _ptr(g.g_view), _ptr(g.g_proj), _ptr(self.g_rot), _ptr(self.g_trans),
+                                                stream), "dgs_testpose_backward_rows")
+        if apply:
+            _lib.check(L.dgs_adam_epoch_step(self._adam, 2, n, g.begin, g.end, pos, scalars, n, 0.9, 0.999, ADAM_EPS, skip,
+                                             stream), "dgs_adam_epoch_step")
+            if g is self.groups[-1]:
+                _lib.check(L.dgs_l2_ema_epoch(_ptr(self.work), pos, n, self._skips, self._begins, len(self.groups),
+                                              _ptr(self.l2_ema), stream), "dgs_l2_ema_epoch")
+
+    @torch.no_grad()
+    def gradients(self):
+        """An epoch WITHOUT its update, enqueued eagerly, at the current parameters (every view's turn taken as the first:
+        no zero-gradient step precedes it): all rows of (dL/drot [n,4], dL/dtrans [n,3]) and the views' (l1, mse) [n,2],
+        as device tensors.  (Also what loads the kernels of the chain before the capture.)"""
+        self.block.copy_(self._zero_block)
+        for g in self.groups:
+            self._enqueue(g, apply=False)
+        return self.g_rot.clone(), self.g_trans.clone(), self.work[:, :2].clone()
+
+    def _capture(self):
+        dev = self.cloud._xyz.device
+        self.gradients()
+        torch.cuda.synchronize(dev)
+        for g in self.groups:
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    self._enqueue(g)
+            except RuntimeError as ex:
+                raise RuntimeError(f"the pose-fit epoch could not be captured into a hipGraph: {ex}") from ex
+            g.graph = graph
+
+    # ------------------------------------------------------------------------------------------------- the fit
+    def schedule(self, orders, first_epoch=0):
+        """Uploads the device schedule of a run -- one row of 5 n words per epoch (epoch_rows) -- and returns the number of
+        epochs.  orders: one view order per epoch (epoch_orders); first_epoch: the StepLR epoch the first of them is."""
+        if any(len(o) != self.n for o in orders):
+            raise ValueError("every epoch's order must be a permutation of the views")
+        rows = epoch_rows(self.steps, orders, first_epoch, self.num_iter_per_view)
+        self._sched = torch.from_numpy(rows).to(self.block.device)
+        self._sched_pos = 0
+        if self.groups[0].graph is None:
+            self._capture()
+        return rows.shape[0]
+
+    def run(self, n_epochs=None):
+        """Enqueues the next n_epochs (default: all remaining) epochs of the uploaded schedule: per epoch one small copy
+        launch (the epoch's row into the device block) and one graph launch per group.  No host synchronisation."""
+        L = _lib.lib()
+        stream = _stream(self.cloud._xyz.device)
+        left = self._sched.shape[0] - self._sched_pos
+        n_epochs = left if n_epochs is None else min(int(n_epochs), left)
+        block = ctypes.c_void_p(self.block.data_ptr())
+        base, words = self._sched.data_ptr(), self.ROW_WORDS * self.n
+        for e in range(self._sched_pos, self._sched_pos + n_epochs):
+            _lib.check(L.dgs_copy_words(block, ctypes.c_void_p(base + 4 * words * e), words, stream), "dgs_copy_words")
+            for g in self.groups:
+                g.graph.replay()
+        self._sched_pos += n_epochs
+        self.steps += n_epochs * self.n
+        return n_epochs
+
+    def dropped(self):
+        """View-steps skipped (a host read): a group whose K = G forward exceeded its capacity skips its rows' whole epoch,
+        G view-steps -- where the sequential fit skips the one step of the view that overflowed."""
+        return sum(int(g.drops.item()) * g.G for g in self.groups)
+
+    def psnr_ema(self):
+        """20 log10(1 / sqrt(l2_error_ema)) as the reference logs it (test.py:183); a host read."""
+        v = float(self.l2_ema.item())
+        return 20.0 * math.log10(1.0 / math.sqrt(v)) if v > 0.0 else float("inf")
+
+    def cameras(self):
+        with torch.no_grad():
+            return [self.model(i) for i in range(self.n)]
+
+
 def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, order=None, seed=None,
-                       log_every=0):
+                       log_every=0, mode="sequential", views_per_call=None, capacity=None):
     """test.py:131-186 on the fused step: fits the test cameras to the cloud and returns the fitted cameras
     ([TestPoseModel(i) for i in range(n)]).  order: see epoch_orders (None: a seeded or global shuffle per epoch).
-    log_every > 0 prints the reference's progress line every that many epochs (one host read each)."""
-    fit = FusedPoseFit(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=num_iter_per_view)
+    log_every > 0 prints the reference's progress line every that many epochs (one host read each).
+    mode: "sequential" (FusedPoseFit: one launch chain per view step) or "epoch" (EpochPoseFit: one per epoch, the same
+    updates; views_per_call caps the views rendered by one call).  capacity: see the two classes (None: learnt)."""
+    if mode not in ("sequential", "epoch"):
+        raise ValueError(f"mode must be 'sequential' or 'epoch' (got {mode!r})")
+    if mode == "epoch":
+        fit = EpochPoseFit(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=num_iter_per_view, capacity=capacity,
+                           views_per_call=views_per_call)
+    else:
+        fit = FusedPoseFit(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=num_iter_per_view, capacity=capacity)
     epochs = int(num_iter_per_view)
     orders = epoch_orders(fit.n, epochs, seed=seed, order=order)
     chunk = int(log_every) if log_every and log_every > 0 else epochs
@@ -393,7 +674,7 @@ def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_vi
     drops = fit.dropped()
     if drops:
         raise RuntimeError(f"{drops} of {fit.steps} pose-fit steps exceeded the duplicate capacity ({fit.capacity}) and "
-                           "were skipped; fit again with FusedPoseFit(capacity=...) sized for the poses it moves through")
+                           f"were skipped; fit again with {type(fit).__name__}(capacity=...) sized for the poses it moves through")
     return fit.cameras()
 
 

@@ -446,6 +446,27 @@ int dgs_adam_scalars(const DgsAdamGroup* groups, int32_t n_groups, double beta1,
 int dgs_adam_step_dev(const DgsAdamGroup* groups, int32_t n_groups, double beta1, double beta2, double eps,
                       double clip_value, const uint32_t* skip_flag, const float* dev_scalars, dgs_stream_t stream);
 
+/* Adam over a whole EPOCH of the test-view pose fit in one launch (evaluation.EpochPoseFit).  The groups are [n, w]
+ * tensors (numel = n w, w <= 64; at most 4 groups) whose row r receives a non-zero gradient at exactly one of the epoch's
+ * n_steps dense steps -- step pos[r] (device int32 [n]; a value outside [0, n_steps) counts as 0) -- and zeros at all
+ * others.  Adam is elementwise and the rows never interact, so the n_steps updates of an element are applied one after
+ * the other by one thread: the statements of dgs_adam_step each time (a zero-gradient step is that update with g = 0:
+ * the moments decay, the parameter moves by its momentum), step j with scalars[j] -- device floats [n_steps, 2 n_groups],
+ * row j = what dgs_adam_scalars writes for step j's count and learning rates.  The lr / step fields are not used.
+ *   peek: for rows [row_begin, row_end), the parameters after the pos[r] zero-gradient steps that precede the row's
+ *         turn -- what the row's gradient has to be evaluated at -- written to peek_out[i] (host array of n_groups device
+ *         tensors shaped like the parameters; only the rows of the range are written).  Reads no gradient, changes no state.
+ *   step: for rows [row_begin, row_end), from the epoch-start state: pos[r] zero-gradient steps, the step with row r of
+ *         `grad`, n_steps - 1 - pos[r] more zero-gradient steps; parameter and both moments written.  Bit-identical to
+ *         n_steps dgs_adam_step_dev launches on dense gradients that are zero outside row order[j] at step j.
+ *         skip_flag (optional device word): non-zero = nothing is written for the whole epoch. */
+int dgs_adam_epoch_peek(const DgsAdamGroup* groups, int32_t n_groups, float* const* peek_out, int32_t n, int32_t row_begin,
+                        int32_t row_end, const int32_t* pos, const float* scalars, int32_t n_steps, double beta1,
+                        double beta2, double eps, dgs_stream_t stream);
+int dgs_adam_epoch_step(const DgsAdamGroup* groups, int32_t n_groups, int32_t n, int32_t row_begin, int32_t row_end,
+                        const int32_t* pos, const float* scalars, int32_t n_steps, double beta1, double beta2, double eps,
+                        const uint32_t* skip_flag, dgs_stream_t stream);
+
 /* Multi-GPU runs (new work, the reference is single-GPU): the local half of a direct reduce-scatter over
  * point-to-point transfers.  `own` [n] is this rank's shard of the gradient bucket, `recv` [world, stride] holds the copy
  * received from every peer in row s = its rank (row `rank` is not read); own <- ((row_0 + row_1) + row_2) + ... with `own`
@@ -523,6 +544,15 @@ int dgs_testpose_forward(const float* rot, const float* trans, const int32_t* id
 int dgs_testpose_backward(const float* rot, const float* trans, const int32_t* idx_dev, int32_t idx, int32_t n,
                           const float* proj, const float* dL_dview, const float* dL_dfull, float* dL_drot,
                           float* dL_dtrans, dgs_stream_t stream);
+/* The same chain for the views [row_begin, row_end) of rot [n,4] / trans [n,3] at once (at most DGS_MAX_K of them): slot
+ * k = row - row_begin of view / full [G,4,4] and campos [G,3]; backward from dL_dview / dL_dfull [G,4,4] into rows
+ * [row_begin, row_end) of dL_drot [n,4] / dL_dtrans [n,3] -- the other rows are NOT written.  One body with the
+ * single-view kernels: every row's results are theirs bit for bit. */
+int dgs_testpose_forward_rows(const float* rot, const float* trans, int32_t n, int32_t row_begin, int32_t row_end,
+                              const float* proj, float* view, float* full, float* campos, dgs_stream_t stream);
+int dgs_testpose_backward_rows(const float* rot, const float* trans, int32_t n, int32_t row_begin, int32_t row_end,
+                               const float* proj, const float* dL_dview, const float* dL_dfull, float* dL_drot,
+                               float* dL_dtrans, dgs_stream_t stream);
 
 /* The loss of one step of that fit (test.py:171-178) for one image x [C,HW]:
  *   y = clamp(tone_map(x), 0, 1);  l1 = mean |y - gt|;  mse = mean (y - gt)^2;  dL_dx = upstream * d l1 / dx
@@ -540,6 +570,22 @@ int dgs_testpose_backward(const float* rot, const float* trans, const int32_t* i
 int dgs_view_loss_grad(const float* x, const float* gt, const int32_t* gt_index_dev, int32_t n_gt, int32_t C, int32_t HW,
                        int32_t tone_mapping, float eps, float bound, const float* upstream, float* dL_dx, float* work,
                        float* l2_ema, const uint32_t* skip_flag, dgs_stream_t stream);
+/* That loss for G = row_end - row_begin images in one launch (at most DGS_MAX_K): image k of x [G,C,HW] against image
+ * row_begin + k of the stack gt [n_gt,C,HW], gradient image k of dL_dx [G,C,HW] (optional), work area k of work [G,12].
+ * Every image gets the block grid dgs_view_loss_grad gives it (a function of C HW only), with the image index on the
+ * grid's second axis, and its own 1 / (C HW): its totals, values and gradient are those of a dgs_view_loss_grad call on
+ * it, bit for bit (a NaN in one image reaches that image's values only). */
+int dgs_view_loss_grad_rows(const float* x, const float* gt, int32_t n_gt, int32_t row_begin, int32_t row_end, int32_t C,
+                            int32_t HW, int32_t tone_mapping, float eps, float bound, const float* upstream, float* dL_dx,
+                            float* work, dgs_stream_t stream);
+/* l2_error_ema over an epoch: l2_ema = 0.6 l2_ema + 0.4 mse_j for the epoch's views IN THE ORDER OF THEIR TURNS, by one
+ * thread.  work [n,12]: the views' work areas by row (word [1] = mse); pos (device int32 [n]): the turn of row r, i.e.
+ * the inverse of the epoch's order (what dgs_adam_epoch_* read; a position outside [0, n) drops its row).  n <= DGS_MAX_K.
+ * Groups (optional, n_groups = 0: none): host arrays skip_flags [n_groups] of device words and group_begin
+ * [n_groups + 1] rising from 0 to n; the rows [group_begin[g], group_begin[g + 1]) do not count when *skip_flags[g] is
+ * non-zero (a NULL word never skips). */
+int dgs_l2_ema_epoch(const float* work, const int32_t* pos, int32_t n, const uint32_t* const* skip_flags,
+                     const int32_t* group_begin, int32_t n_groups, float* l2_ema, dgs_stream_t stream);
 
 /* PSNR and SSIM of two [3,H,W] images as the reference's evaluation computes them (test.py:118-119):
  * out[0] = mean over the three channels of 20 log10(1 / sqrt(mse_c)) (utils/image_utils.py:17-19),

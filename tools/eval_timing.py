@@ -3,6 +3,9 @@
   fit      ms per step of the fused test-view pose fit (evaluation.FusedPoseFit: one hipGraph replay per step) against
            ms per step of the same fit driven through render(), autograd and torch.optim.Adam
            (tests/autograd_pose_fit.py: the only way to run it before ABI 15)
+  epoch_fit  ms per EPOCH of that fit at n = 3, 8 and 16 test views: the sequential FusedPoseFit (n graph replays per
+           epoch) against the epoch-fused EpochPoseFit (one K = n launch chain per epoch), same scene, same schedule,
+           same repetition scheme (20 epochs of warm-up, 50 epochs between two device events)
   stages   the context's stage timers of dgs_backward_pose_only against dgs_backward on the same forward state, at
            K = 1 and at K = 15
   metrics  ms per dgs_image_metrics call (PSNR + SSIM of two 1080p images)
@@ -24,7 +27,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-LEGS = [("fit", 420), ("stages_k1", 240), ("stages_k15", 300), ("metrics", 120)]
+LEGS = [("fit", 420), ("epoch_fit", 600), ("stages_k1", 240), ("stages_k15", 300), ("metrics", 120)]
 
 
 def _scene(P, K):
@@ -32,24 +35,24 @@ def _scene(P, K):
     return synthetic.make_config("metric", seed=0, P=P, K=K)
 
 
-def _fit_setup(P):
+def _fit_setup(P, n=3):
     import numpy as np
     import torch
     from scipy.spatial.transform import Rotation
     from deblurgs_amd import evaluation as ev, gaussian_renderer, losses
     from deblurgs_amd.cloud import GaussianCloud
-    sc = _scene(P, 3)
+    sc = _scene(P, n)
     cloud = GaussianCloud.from_scene(sc, "cuda")
     tm = losses.ToneMapping("gamma")
     bg = torch.tensor([0.2, 0.3, 0.1], device="cuda")
-    V = sc["viewmatrix"][:3].astype(np.float64)
+    V = sc["viewmatrix"][:n].astype(np.float64)
     W, H = sc["W"], sc["H"]
     cam = lambda R, T: ev.TestCamera(R, T, sc["FoVx"], sc["FoVy"], W, H)
-    truth = ev.TestPoseModel([cam(V[i][:3, :3], V[i][3, :3]) for i in range(3)], device="cuda")
+    truth = ev.TestPoseModel([cam(V[i][:3, :3], V[i][3, :3]) for i in range(n)], device="cuda")
     with torch.no_grad():
-        gts = torch.stack([tm(gaussian_renderer.render(truth(i), cloud, bg)["render"]).clamp(0.0, 1.0) for i in range(3)])
+        gts = torch.stack([tm(gaussian_renderer.render(truth(i), cloud, bg)["render"]).clamp(0.0, 1.0) for i in range(n)])
     dR = Rotation.from_rotvec(np.deg2rad(0.3) * np.array([0.6, -0.64, 0.48])).as_matrix()
-    start = [cam(V[i][:3, :3] @ dR, V[i][3, :3] + np.array([0.02, -0.01, 0.02])) for i in range(3)]
+    start = [cam(V[i][:3, :3] @ dR, V[i][3, :3] + np.array([0.02, -0.01, 0.02])) for i in range(n)]
     return cloud, start, gts, bg, tm
 
 
@@ -85,6 +88,46 @@ def leg_fit(P):
             "fused_host_enqueue_ms_per_step": t_enqueue * 1e3 / n_fused, "autograd_ms_per_step": auto_ms,
             "speedup": auto_ms / fused_ms, "fused_steps_timed": n_fused, "autograd_steps_timed": n_auto,
             "capacity": fit.capacity, "dropped": fit.dropped(), "l1_after_fused_steps": l1_fused}
+
+
+def leg_epoch_fit(P, views=(3, 8, 16), warm=20, reps=50):
+    """ms per epoch, sequential against epoch-fused, at each number of views; both fits run the same schedule from the same
+    start, so their parameters after the timed epochs are compared as well."""
+    import torch
+    from deblurgs_amd import evaluation as ev
+    out = {"P": P, "warmup_epochs": warm, "timed_epochs": reps, "by_views": {}}
+    for n in views:
+        cloud, start, gts, bg, tm = _fit_setup(P, n)
+        orders = ev.epoch_orders(n, warm + reps, order=list(range(n)))
+        res = {}
+        fits = {}
+        for name, cls, unit in (("sequential", ev.FusedPoseFit, n), ("epoch", ev.EpochPoseFit, 1)):
+            fit = cls(cloud, start, gts, bg, tm, num_iter_per_view=2000)
+            fit.schedule(orders)
+            fit.run(warm * unit)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            fit.run(reps * unit)
+            e1.record()
+            t_enqueue = time.perf_counter() - t0
+            torch.cuda.synchronize()
+            res[name + "_ms_per_epoch"] = e0.elapsed_time(e1) / reps
+            res[name + "_host_enqueue_ms_per_epoch"] = t_enqueue * 1e3 / reps
+            res[name + "_dropped"] = fit.dropped()
+            res[name + "_capacity"] = fit.capacity
+            fits[name] = fit
+        a, b = fits["sequential"], fits["epoch"]
+        res["speedup"] = res["sequential_ms_per_epoch"] / res["epoch_ms_per_epoch"]
+        res["parameters_bit_identical"] = bool(torch.equal(a.model._rot, b.model._rot) and torch.equal(a.model._trans, b.model._trans))
+        res["max_abs_diff_rot"] = float((a.model._rot.detach() - b.model._rot.detach()).abs().max())
+        res["max_abs_diff_trans"] = float((a.model._trans.detach() - b.model._trans.detach()).abs().max())
+        out["by_views"][str(n)] = res
+        print("epoch_fit", n, json.dumps(res), file=sys.stderr, flush=True)
+        del fits, a, b, fit, cloud, gts
+        torch.cuda.empty_cache()
+    return out
 
 
 def leg_stages(P, K):
@@ -165,7 +208,7 @@ def main():
     ap.add_argument("--leg", default=None, help="internal: run one leg in this process and print its JSON")
     a = ap.parse_args()
     if a.leg is not None:
-        res = {"fit": lambda: leg_fit(a.P), "stages_k1": lambda: leg_stages(a.P, 1),
+        res = {"fit": lambda: leg_fit(a.P), "epoch_fit": lambda: leg_epoch_fit(a.P), "stages_k1": lambda: leg_stages(a.P, 1),
                "stages_k15": lambda: leg_stages(a.P, 15), "metrics": lambda: leg_metrics(a.P)}[a.leg]()
         print("EVAL_TIMING_JSON " + json.dumps(res), flush=True)
         return 0
