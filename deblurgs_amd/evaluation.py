@@ -6,8 +6,9 @@ number the reference reports comes from
                                            CAMERA only, one Adam step on a quaternion and a translation
     evaluate             test.py:93-129    PSNR / SSIM (/ LPIPS) of the renders at the fitted cameras
 
-`TestPoseModel` is OptimPoseModel (test.py:39-91).  `FusedPoseFit` is one step of the fit enqueued straight through the C
-ABI and replayed as ONE captured hipGraph -- no autograd, no host read:
+`TestPoseModel` is OptimPoseModel (test.py:39-91).  Both fits share `_PoseFit` (checks, ground truth, Adam's state, capture
+and replay) and hold the state of a rasteriser call in a `_RasterCall`.  `FusedPoseFit` is one step of the fit enqueued
+straight through the C ABI and replayed as ONE captured hipGraph -- no autograd, no host read:
 
     quaternion + translation of the drawn view -> camera     dgs_testpose_forward   (view index from device memory)
     K = 1 rasterisation of the cloud's raw parameters        dgs_forward            (capacity sized ahead)
@@ -24,12 +25,11 @@ Semantics are the reference's: Adam (rates 5e-5 / 5e-4, eps 1e-15) runs over the
 (rows with zero gradient still move by their momentum, as torch's dense Adam moves them), StepLR(num_iter // 20, 0.9)
 advances once per epoch, an epoch visits every view once in shuffled order.
 
-`EpochPoseFit` (opt-in: optimize_test_pose(mode="epoch")) runs the same fit with ONE launch chain per epoch instead of one
-per view: all n views of an epoch go through one K = n rasteriser call (or one call per group of `views_per_call` rows).
-No update changes.  Adam is elementwise, row i of `_rot` / `_trans` gets a non-zero gradient only at view i's turn, and
-that gradient depends on row i alone; so within an epoch with order o, row i at position p_i sees p_i zero-gradient
-steps (it still moves by its momentum), one real step at the parameters it has THEN, and n - 1 - p_i more zero-gradient
-steps, each with that global step's bias corrections -- and rows never interact.  The chain of a group of rows is
+`EpochPoseFit` (opt-in: optimize_test_pose(mode="epoch")) runs the same fit with ONE launch chain per epoch and group of
+`views_per_call` rows (default: all n views in one K = n call).  No update changes: Adam is elementwise, and row i of
+`_rot` / `_trans` gets a non-zero gradient only at view i's turn, from row i alone; so a row at position p of the epoch's
+order sees p zero-gradient steps (it still moves by its momentum), one real step at the parameters it has THEN, and
+n - 1 - p more zero-gradient steps, each with that global step's bias corrections.  The chain of a group of rows is
 
     parameters of every row at ITS turn (p_i zero-gradient steps)   dgs_adam_epoch_peek
     -> the G cameras                                                dgs_testpose_forward_rows
@@ -180,11 +180,9 @@ def step_lrs(epochs, num_iter_per_view):
 
 
 def _capacity_for(need):
-    """The capacity for poses that need `need` duplicates at the start: half as much again + 16384, rounded up to 1/32 of
-    its leading power of two (at least 1024)."""
-    cap = need + need // 2 + 16384
-    q = 1 << max(cap.bit_length() - 5, 10)
-    return -(-cap // q) * q
+    """The capacity for poses that need `need` duplicates at the start: half as much again + 16384, rounded up as every
+    learnt capacity is (raster_call.round_capacity)."""
+    return raster_call.round_capacity(need + need // 2 + 16384)
 
 
 def step_rows(steps_done, orders, first_epoch, num_iter_per_view):
@@ -225,30 +223,73 @@ def epoch_rows(steps_done, orders, first_epoch, num_iter_per_view):
     return rows
 
 
-class FusedPoseFit:
-    HYPER_WORDS = 8      # [0] view index (int32), [1:5] Adam's (-(lr / (1 - beta1^t)), sqrt(1 - beta2^t)) for rot, trans
+class _RasterCall:
+    """The buffers, blobs, structs, capacity and captured graph of one K = G rasteriser call of a fit, over rows
+    [begin, end) of its views.  Everything is allocated once: the captured graph bakes the addresses in."""
 
-    def __init__(self, cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, model=None, tile_cull=None,
-                 capacity=None):
-        """cloud: a GaussianCloud (fused_activations); cams: the test cameras (all of one image size and field of view);
-        gt_images: [n,3,H,W] or a list of [3,H,W]; bg: [3]; tone_mapping: losses.ToneMapping("identity" | "gamma") or its
-        name.  capacity: duplicates the lists are sized for (None: 1.5 x the largest count over the views at their
-        start poses + 16384, learnt with one exact forward per view here, outside the loop)."""
+    def __init__(self, fit, begin, end, capacity):
+        self.begin, self.end, self.G = begin, end, end - begin
+        self.graph = None
+        G, H, W, P = self.G, fit.H, fit.W, fit.cloud._xyz.shape[0]
+        dev = fit.cloud._xyz.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        self.view, self.full = torch.empty((G, 4, 4), **f32), torch.empty((G, 4, 4), **f32)
+        self.campos = torch.empty((G, 3), **f32)
+        self.color, self.dcolor = torch.empty((G, 3, H, W), **f32), torch.empty((G, 3, H, W), **f32)
+        self.radii = torch.empty((G, P), dtype=torch.int32, device=dev)
+        self.drops = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.g_view, self.g_proj = torch.empty((G, 4, 4), **f32), torch.empty((G, 4, 4), **f32)
+        self.host = torch.zeros(8, dtype=torch.int32).pin_memory()
+        self.geom = torch.empty(L.dgs_geom_state_bytes(P, G), dtype=torch.uint8, device=dev)
+        self.image = torch.empty(L.dgs_image_state_bytes(W, H, G), dtype=torch.uint8, device=dev)
+        self.out_probe = raster_call.forward_out(self.color, None, self.radii, self.host)     # skips nothing, counts nothing
+        self.capacity = int(capacity) if capacity is not None else _capacity_for(fit._duplicates(self))
+        self.binning = torch.empty(L.dgs_binning_state_bytes(self.capacity, W, H, G), dtype=torch.uint8, device=dev)
+        self.scratch = torch.empty(L.dgs_backward_scratch_bytes(self.capacity, P, G), dtype=torch.uint8, device=dev)
+        self.skip_ptr = self.geom.data_ptr() + raster_call.skip_word_offset(P, W, H, G)
+        self.prob = self.problem(fit, self.binning)
+        self.out = raster_call.forward_out(self.color, None, self.radii, self.host, drop_counter=self.drops)
+        self.io = _lib.DgsBackwardIO()
+        self.io.num_rendered = self.capacity
+        self.io.radii, self.io.dL_dout_color = _ptr(self.radii), _ptr(self.dcolor)
+        self.io.scratch, self.io.scratch_bytes = _ptr(self.scratch), self.scratch.numel()
+        self.io.dL_dviewmatrix, self.io.dL_dprojmatrix = _ptr(self.g_view), _ptr(self.g_proj)
+
+    def problem(self, fit, binning=None):
+        c0 = fit.model.cams[0]
+        return raster_call.cloud_problem(fit.cloud, self.G, self.view, self.full, self.campos, fit.H, fit.W, c0.FoVx, c0.FoVy,
+                                         fit.bg, fit.cull, self.geom, self.image, binning)
+
+    def exact_count(self, fit):
+        """The duplicate count of one exact (two-phase) forward at the cameras the call's buffers hold; a host read."""
+        R, _ = raster_call.forward(fit.cloud._xyz.device, self.problem(fit), self.out_probe, self.host, None)
+        return int(R)
+
+
+class _PoseFit:
+    """What the two fits share: the checks, the pose model, the ground truth, Adam's state, one _RasterCall per group of
+    rows (`groups`), the capture of every group's launch chain, and the replay of an uploaded schedule.  A subclass
+    gives the row ranges of its groups (_ranges), the duplicate count a group's lists are sized from (_duplicates), its
+    device block and work area, its schedule rows, its chain (_enqueue), gradients() and dropped()."""
+
+    def __init__(self, cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view, model, tile_cull, capacity):
+        name = type(self).__name__
         if not getattr(cloud, "fused_activations", False):
-            raise NotImplementedError("FusedPoseFit needs a cloud with fused_activations")
+            raise NotImplementedError(f"{name} needs a cloud with fused_activations")
         self.cloud = cloud
         dev = cloud._xyz.device
         if dev.type != "cuda":
-            raise RuntimeError("FusedPoseFit needs a cloud on a HIP device (no CPU fallback)")
-        self.model = model if model is not None else TestPoseModel(cams, device=dev)
-        m = self.model
+            raise RuntimeError(f"{name} needs a cloud on a HIP device (no CPU fallback)")
+        self.model = m = model if model is not None else TestPoseModel(cams, device=dev)
         self.n = n = len(m)
+        ranges = self._ranges()
         c0 = m.cams[0]
         for c in m.cams:
             if (c.image_width, c.image_height, c.FoVx, c.FoVy, c.znear, c.zfar) != \
                     (c0.image_width, c0.image_height, c0.FoVx, c0.FoVy, c0.znear, c0.zfar):
-                raise NotImplementedError("FusedPoseFit captures one step for all views: they must share image size and "
-                                          "intrinsics (fit views of different sizes with one FusedPoseFit each)")
+                raise NotImplementedError(f"{name} captures one launch chain for all views: they must share image size and "
+                                          f"intrinsics (fit views of different sizes with one {name} each)")
         self.H, self.W = H, W = int(c0.image_height), int(c0.image_width)
         self.num_iter_per_view = int(num_iter_per_view)
         self.tone_mapping, self._tone, self._eps, self._bound = _tone_args(tone_mapping)
@@ -262,158 +303,58 @@ class FusedPoseFit:
         self.cull = dgr.TILE_CULL if tile_cull is None else bool(tile_cull)
         self.steps = 0                # Adam steps enqueued so far (the bias-correction exponent)
         self._sched = None
-        self._graph = None
-        P = cloud._xyz.shape[0]
-        L = _lib.lib()
-        # ---- every buffer of the step, allocated once: the captured graph bakes their addresses in
-        self.hyper = torch.zeros(self.HYPER_WORDS, **f32)
-        self.view, self.full, self.campos = torch.empty((1, 4, 4), **f32), torch.empty((1, 4, 4), **f32), torch.empty((1, 3), **f32)
-        self.color = torch.empty((1, 3, H, W), **f32)
-        self.dcolor = torch.empty((1, 3, H, W), **f32)
-        self.radii = torch.empty((1, P), dtype=torch.int32, device=dev)
-        self.work = torch.zeros(12, **f32)           # dgs_view_loss_grad's work area: [0] l1, [1] mse
-        self.l2_ema = torch.zeros(1, **f32)          # the reference's l2_error_ema, on the device
-        self.drops = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.g_view, self.g_proj = torch.empty((1, 4, 4), **f32), torch.empty((1, 4, 4), **f32)
-        self.g_rot, self.g_trans = torch.empty((n, 4), **f32), torch.empty((n, 3), **f32)
+        # ---- what all groups share: the dense gradients (zero-filled: a rows kernel writes only its own rows), the
+        # reference's l2_error_ema on the device, Adam's moments
+        self.g_rot, self.g_trans = torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)
+        self.l2_ema = torch.zeros(1, **f32)
         self.exp_avg = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
         self.exp_avg_sq = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
-        self._host = torch.zeros(8, dtype=torch.int32).pin_memory()
-        self._geom = torch.empty(L.dgs_geom_state_bytes(P, 1), dtype=torch.uint8, device=dev)
-        self._image = torch.empty(L.dgs_image_state_bytes(W, H, 1), dtype=torch.uint8, device=dev)
-        self.capacity = int(capacity) if capacity is not None else self._learn_capacity()
-        self._binning = torch.empty(L.dgs_binning_state_bytes(self.capacity, W, H, 1), dtype=torch.uint8, device=dev)
-        self._scratch = torch.empty(L.dgs_backward_scratch_bytes(self.capacity, P, 1), dtype=torch.uint8, device=dev)
-        self._skip_ptr = self._geom.data_ptr() + raster_call.skip_word_offset(P, W, H, 1)
-        self._prob, self._out, self._io, self._groups = self._structs()
-
-    # ------------------------------------------------------------------------------------------------ plumbing
-    def _settings(self):
-        cloud, c0 = self.cloud, self.model.cams[0]
-        return dgr.GaussianRasterizationSettings(
-            image_height=self.H, image_width=self.W, tanfovx=math.tan(c0.FoVx * 0.5), tanfovy=math.tan(c0.FoVy * 0.5),
-            bg=self.bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
-            sh_degree=cloud.active_sh_degree, campos=self.campos, prefiltered=False, debug=False)
-
-    def _problem(self, binning=None):
-        cloud = self.cloud
-        rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
-        raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
-        return raster_call.problem(1, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
-                                   None, self.view, self.full, self.campos, self._settings(), self.bg, self.cull, 0, raw=raw,
-                                   geom=self._geom, image=self._image, binning=binning)
-
-    def _pose_forward(self, idx_dev, idx, stream):
-        m = self.model
-        _lib.check(_lib.lib().dgs_testpose_forward(_ptr(m._rot), _ptr(m._trans), idx_dev, int(idx), self.n, _ptr(self.proj),
-                                                   _ptr(self.view), _ptr(self.full), _ptr(self.campos), stream),
-                   "dgs_testpose_forward")
-
-    @torch.no_grad()
-    def _learn_capacity(self):
-        """One exact (two-phase) forward per view at its start pose: the largest duplicate count, with half as much again
-        for the poses the fit moves through."""
-        dev = self.cloud._xyz.device
-        need = 0
-        for i in range(self.n):
-            self._pose_forward(None, i, _stream(dev))
-            prob = self._problem()
-            out = raster_call.forward_out(self.color, None, self.radii, self._host)
-            R, _ = raster_call.forward(dev, prob, out, self._host, None)
-            need = max(need, int(R))
-        return _capacity_for(need)
-
-    def _structs(self):
-        m = self.model
-        prob = self._problem(self._binning)
-        out = raster_call.forward_out(self.color, None, self.radii, self._host, drop_counter=self.drops)
-        io = _lib.DgsBackwardIO()
-        io.num_rendered = self.capacity
-        io.radii, io.dL_dout_color = _ptr(self.radii), _ptr(self.dcolor)
-        io.scratch, io.scratch_bytes = _ptr(self._scratch), self._scratch.numel()
-        io.dL_dviewmatrix, io.dL_dprojmatrix = _ptr(self.g_view), _ptr(self.g_proj)
-        groups = (_lib.DgsAdamGroup * 2)(
+        self._adam = (_lib.DgsAdamGroup * 2)(
             _lib.DgsAdamGroup(m._rot.data_ptr(), self.g_rot.data_ptr(), self.exp_avg[0].data_ptr(),
                               self.exp_avg_sq[0].data_ptr(), m._rot.numel(), ROT_LR, 1),
             _lib.DgsAdamGroup(m._trans.data_ptr(), self.g_trans.data_ptr(), self.exp_avg[1].data_ptr(),
                               self.exp_avg_sq[1].data_ptr(), m._trans.numel(), TRANS_LR, 1))
-        return prob, out, io, groups
-
-    @torch.no_grad()
-    def _enqueue(self, apply=True):
-        """The six launches of one step on the current stream, everything read from the device block `hyper`."""
-        L = _lib.lib()
-        m = self.model
-        dev = self.cloud._xyz.device
-        stream = _stream(dev)
-        idx_dev = ctypes.c_void_p(self.hyper.data_ptr())
-        skip = ctypes.c_void_p(self._skip_ptr)
-        self._pose_forward(idx_dev, 0, stream)
-        _lib.check(L.dgs_forward(ctypes.byref(self._prob), ctypes.byref(self._out), self.capacity, stream), "dgs_forward")
-        _lib.check(L.dgs_view_loss_grad(_ptr(self.color), _ptr(self.gt), idx_dev, self.n, 3, self.H * self.W, self._tone, self._eps,
-                                        self._bound, None, _ptr(self.dcolor), _ptr(self.work),
-                                        _ptr(self.l2_ema) if apply else None, skip, stream), "dgs_view_loss_grad")
-        _lib.check(L.dgs_backward_pose_only(ctypes.byref(self._prob), ctypes.byref(self._io), stream),
-                   "dgs_backward_pose_only")
-        _lib.check(L.dgs_testpose_backward(_ptr(m._rot), _ptr(m._trans), idx_dev, 0, self.n, _ptr(self.proj),
-                                           _ptr(self.g_view), _ptr(self.g_proj), _ptr(self.g_rot), _ptr(self.g_trans),
-                                           stream), "dgs_testpose_backward")
-        if apply:
-            _lib.check(L.dgs_adam_step_dev(self._groups, 2, 0.9, 0.999, ADAM_EPS, 0.0, skip,
-                                           ctypes.c_void_p(self.hyper.data_ptr() + 4), stream), "dgs_adam_step_dev")
-
-    @torch.no_grad()
-    def gradients(self, idx):
-        """One step WITHOUT its update, enqueued eagerly: the dense (dL/drot [n,4], dL/dtrans [n,3]) of view idx and the
-        loss values (l1, mse) as device tensors.  (Also what loads every kernel of the step before the capture.)"""
-        self.hyper[:1].copy_(torch.tensor([int(idx)], dtype=torch.int32).view(torch.float32))
-        self._enqueue(apply=False)
-        return self.g_rot.clone(), self.g_trans.clone(), self.work[:2].clone()
+        # ---- per group: the cameras, images, lists and gradient matrices of its K = G call
+        self.groups = [_RasterCall(self, b, e, capacity) for b, e in ranges]
+        self.capacity = max(g.capacity for g in self.groups)
 
     def _capture(self):
-        dev = self.cloud._xyz.device
-        self.gradients(0)                     # every kernel of the step has run once: nothing is loaded inside the capture
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                self._enqueue()
-        except RuntimeError as ex:
-            raise RuntimeError(f"the pose-fit step could not be captured into a hipGraph: {ex}") from ex
-        self._graph = graph
+        self.block.zero_()                    # view 0 / every view's turn the first
+        for g in self.groups:                 # every kernel of the chain has run once: nothing is loaded inside the capture
+            self._enqueue(g, apply=False)
+        torch.cuda.synchronize(self.block.device)
+        for g in self.groups:
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    self._enqueue(g)
+            except RuntimeError as ex:
+                raise RuntimeError(f"the pose-fit launch chain could not be captured into a hipGraph: {ex}") from ex
+            g.graph = graph
 
-    # ------------------------------------------------------------------------------------------------- the fit
-    def schedule(self, orders, first_epoch=0):
-        """Uploads the device schedule of a run -- one 8-word row per step: the view index and Adam's scalars for the
-        step's count and its epoch's learning rates -- and returns the number of steps.  orders: one view order per
-        epoch (epoch_orders); first_epoch: the StepLR epoch the first of them is."""
-        rows = step_rows(self.steps, orders, first_epoch, self.num_iter_per_view)
-        self._sched = torch.from_numpy(rows).to(self.hyper.device)
+    def _upload(self, rows):
+        """The device schedule of a run, one row of the device block per replay; returns the number of rows."""
+        self._sched = torch.from_numpy(rows).to(self.block.device)
         self._sched_pos = 0
-        if self._graph is None:
+        if self.groups[0].graph is None:
             self._capture()
         return rows.shape[0]
 
-    def run(self, n_steps=None):
-        """Enqueues the next n_steps (default: all remaining) steps of the uploaded schedule: per step one small copy
-        launch (the step's row into the device block) and one graph launch.  No host synchronisation."""
+    def _replay(self, n_rows=None):
+        """Enqueues the next n_rows (default: all remaining) rows of the uploaded schedule: per row one small copy launch
+        (the row into the device block) and one graph launch per group.  No host synchronisation."""
         L = _lib.lib()
-        dev = self.cloud._xyz.device
-        stream = _stream(dev)
+        stream = _stream(self.block.device)
         left = self._sched.shape[0] - self._sched_pos
-        n_steps = left if n_steps is None else min(int(n_steps), left)
-        hyper = ctypes.c_void_p(self.hyper.data_ptr())
-        base, words = self._sched.data_ptr(), self.HYPER_WORDS
-        for i in range(self._sched_pos, self._sched_pos + n_steps):
-            _lib.check(L.dgs_copy_words(hyper, ctypes.c_void_p(base + 4 * words * i), words, stream), "dgs_copy_words")
-            self._graph.replay()
-        self._sched_pos += n_steps
-        self.steps += n_steps
-        return n_steps
-
-    def dropped(self):
-        """Steps whose duplicate count exceeded the capacity (a host read): their update was skipped on the device."""
-        return int(self.drops.item())
+        n_rows = left if n_rows is None else min(int(n_rows), left)
+        block = ctypes.c_void_p(self.block.data_ptr())
+        base, words = self._sched.data_ptr(), self.block.numel()
+        for i in range(self._sched_pos, self._sched_pos + n_rows):
+            _lib.check(L.dgs_copy_words(block, ctypes.c_void_p(base + 4 * words * i), words, stream), "dgs_copy_words")
+            for g in self.groups:
+                g.graph.replay()
+        self._sched_pos += n_rows
+        return n_rows
 
     def psnr_ema(self):
         """20 log10(1 / sqrt(l2_error_ema)) as the reference logs it (test.py:183); a host read."""
@@ -425,15 +366,88 @@ class FusedPoseFit:
             return [self.model(i) for i in range(self.n)]
 
 
-class _EpochGroup:
-    """The buffers, structs and captured graph of one group of rows [begin, end) of an EpochPoseFit."""
+class FusedPoseFit(_PoseFit):
+    """The sequential fit (module docstring): one K = 1 launch chain per view step, its view drawn from the device block."""
+    HYPER_WORDS = 8      # [0] view index (int32), [1:5] Adam's (-(lr / (1 - beta1^t)), sqrt(1 - beta2^t)) for rot, trans
 
-    def __init__(self, begin, end):
-        self.begin, self.end, self.G = begin, end, end - begin
-        self.graph = None
+    def __init__(self, cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, model=None, tile_cull=None,
+                 capacity=None):
+        """cloud: a GaussianCloud (fused_activations); cams: the test cameras (all of one image size and field of view);
+        gt_images: [n,3,H,W] or a list of [3,H,W]; bg: [3]; tone_mapping: losses.ToneMapping("identity" | "gamma") or its
+        name.  capacity: duplicates the lists are sized for (None: 1.5 x the largest count over the views at their
+        start poses + 16384, learnt with one exact forward per view here, outside the loop)."""
+        super().__init__(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view, model, tile_cull, capacity)
+        f32 = dict(dtype=torch.float32, device=cloud._xyz.device)
+        self.block = torch.zeros(self.HYPER_WORDS, **f32)
+        self.work = torch.zeros(12, **f32)           # dgs_view_loss_grad's work area: [0] l1, [1] mse
+
+    color = property(lambda self: self.groups[0].color)      # the [1,3,H,W] render of the last step
+
+    def _ranges(self):
+        return [(0, 1)]
+
+    def _pose_forward(self, g, idx_dev, idx, stream):
+        m = self.model
+        _lib.check(_lib.lib().dgs_testpose_forward(_ptr(m._rot), _ptr(m._trans), idx_dev, int(idx), self.n, _ptr(self.proj),
+                                                   _ptr(g.view), _ptr(g.full), _ptr(g.campos), stream),
+                   "dgs_testpose_forward")
+
+    @torch.no_grad()
+    def _duplicates(self, g):
+        """One exact forward per view at its start pose: the largest duplicate count."""
+        need = 0
+        for i in range(self.n):
+            self._pose_forward(g, None, i, _stream(self.cloud._xyz.device))
+            need = max(need, g.exact_count(self))
+        return need
+
+    @torch.no_grad()
+    def _enqueue(self, g, apply=True):
+        """The six launches of one step on the current stream, everything read from the device block."""
+        L = _lib.lib()
+        m = self.model
+        stream = _stream(self.cloud._xyz.device)
+        idx_dev = ctypes.c_void_p(self.block.data_ptr())
+        skip = ctypes.c_void_p(g.skip_ptr)
+        self._pose_forward(g, idx_dev, 0, stream)
+        _lib.check(L.dgs_forward(ctypes.byref(g.prob), ctypes.byref(g.out), g.capacity, stream), "dgs_forward")
+        _lib.check(L.dgs_view_loss_grad(_ptr(g.color), _ptr(self.gt), idx_dev, self.n, 3, self.H * self.W, self._tone,
+                                        self._eps, self._bound, None, _ptr(g.dcolor), _ptr(self.work),
+                                        _ptr(self.l2_ema) if apply else None, skip, stream), "dgs_view_loss_grad")
+        _lib.check(L.dgs_backward_pose_only(ctypes.byref(g.prob), ctypes.byref(g.io), stream), "dgs_backward_pose_only")
+        _lib.check(L.dgs_testpose_backward(_ptr(m._rot), _ptr(m._trans), idx_dev, 0, self.n, _ptr(self.proj),
+                                           _ptr(g.g_view), _ptr(g.g_proj), _ptr(self.g_rot), _ptr(self.g_trans),
+                                           stream), "dgs_testpose_backward")
+        if apply:
+            _lib.check(L.dgs_adam_step_dev(self._adam, 2, 0.9, 0.999, ADAM_EPS, 0.0, skip,
+                                           ctypes.c_void_p(self.block.data_ptr() + 4), stream), "dgs_adam_step_dev")
+
+    @torch.no_grad()
+    def gradients(self, idx):
+        """One step WITHOUT its update, enqueued eagerly: the dense (dL/drot [n,4], dL/dtrans [n,3]) of view idx and the
+        loss values (l1, mse) as device tensors."""
+        self.block[:1].copy_(torch.tensor([int(idx)], dtype=torch.int32).view(torch.float32))
+        self._enqueue(self.groups[0], apply=False)
+        return self.g_rot.clone(), self.g_trans.clone(), self.work[:2].clone()
+
+    def schedule(self, orders, first_epoch=0):
+        """Uploads the device schedule of a run -- one 8-word row per step: the view index and Adam's scalars for the
+        step's count and its epoch's learning rates -- and returns the number of steps.  orders: one view order per
+        epoch (epoch_orders); first_epoch: the StepLR epoch the first of them is."""
+        return self._upload(step_rows(self.steps, orders, first_epoch, self.num_iter_per_view))
+
+    def run(self, n_steps=None):
+        """Enqueues the next n_steps (default: all remaining) steps of the uploaded schedule (_replay)."""
+        n_steps = self._replay(n_steps)
+        self.steps += n_steps
+        return n_steps
+
+    def dropped(self):
+        """Steps whose duplicate count exceeded the capacity (a host read): their update was skipped on the device."""
+        return int(self.groups[0].drops.item())
 
 
-class EpochPoseFit:
+class EpochPoseFit(_PoseFit):
     """The fit of FusedPoseFit with one launch chain per epoch and group of rows (module docstring): the same updates,
     n times fewer chains.  views_per_call: None = all n views in one K = n call; a number caps the views per call (memory:
     every call holds its own K = G images and lists) -- consecutive row groups of that size, each its own chain, buffers
@@ -444,99 +458,28 @@ class EpochPoseFit:
                  capacity=None, views_per_call=None):
         """As FusedPoseFit.  capacity: duplicates EVERY group's lists are sized for (None: per group, 1.5 x the count of one
         exact K = G forward at the start poses + 16384, rounded up as FusedPoseFit rounds)."""
-        if not getattr(cloud, "fused_activations", False):
-            raise NotImplementedError("EpochPoseFit needs a cloud with fused_activations")
-        self.cloud = cloud
-        dev = cloud._xyz.device
-        if dev.type != "cuda":
-            raise RuntimeError("EpochPoseFit needs a cloud on a HIP device (no CPU fallback)")
-        self.model = model if model is not None else TestPoseModel(cams, device=dev)
-        m = self.model
-        self.n = n = len(m)
-        if n > _lib.DGS_MAX_K:
-            raise NotImplementedError(f"EpochPoseFit fits at most DGS_MAX_K = {_lib.DGS_MAX_K} views (got {n}): an epoch's "
-                                      "schedule is one device block; use the sequential fit")
-        c0 = m.cams[0]
-        for c in m.cams:
-            if (c.image_width, c.image_height, c.FoVx, c.FoVy, c.znear, c.zfar) != \
-                    (c0.image_width, c0.image_height, c0.FoVx, c0.FoVy, c0.znear, c0.zfar):
-                raise NotImplementedError("EpochPoseFit renders the views of an epoch in one call: they must share image "
-                                          "size and intrinsics")
-        per_call = n if views_per_call is None else int(views_per_call)
-        if per_call < 1:
-            raise ValueError("views_per_call must be at least 1")
-        per_call = min(per_call, n)
-        self.H, self.W = H, W = int(c0.image_height), int(c0.image_width)
-        self.num_iter_per_view = int(num_iter_per_view)
-        self.tone_mapping, self._tone, self._eps, self._bound = _tone_args(tone_mapping)
-        f32 = dict(dtype=torch.float32, device=dev)
-        gt = torch.stack(list(gt_images)) if not torch.is_tensor(gt_images) else gt_images
-        self.gt = gt.to(**f32).contiguous()
-        if tuple(self.gt.shape) != (n, 3, H, W):
-            raise ValueError(f"gt_images must be [{n},3,{H},{W}]")
-        self.bg = bg.to(**f32).contiguous()
-        self.proj = m.projection_matrix(0).to(**f32).contiguous()
-        self.cull = dgr.TILE_CULL if tile_cull is None else bool(tile_cull)
-        self.steps = 0                # Adam steps enqueued so far: epochs x n
-        self._sched = None
-        P = cloud._xyz.shape[0]
-        L = _lib.lib()
-        # ---- what all groups share (each writes its own rows): the epoch's device block, the turn-time parameters, the
-        # gradients, the work areas, Adam's moments
+        self._per_call = views_per_call
+        super().__init__(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view, model, tile_cull, capacity)
+        n = self.n
+        f32 = dict(dtype=torch.float32, device=cloud._xyz.device)
+        # (each group writes its own rows of the turn-time parameters and of the work areas)
         self.block = torch.zeros(self.ROW_WORDS * n, **f32)      # [0:n] pos (int32), [n:5n] the [n,4] scalars
-        self._zero_block = torch.zeros_like(self.block)
         self.peek = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
-        self.g_rot, self.g_trans = torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)
         self.work = torch.zeros((n, 12), **f32)      # dgs_view_loss_grad_rows' work areas by row: [r,0] l1, [r,1] mse
-        self.l2_ema = torch.zeros(1, **f32)
-        self.exp_avg = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
-        self.exp_avg_sq = [torch.zeros((n, 4), **f32), torch.zeros((n, 3), **f32)]
-        self._adam = (_lib.DgsAdamGroup * 2)(
-            _lib.DgsAdamGroup(m._rot.data_ptr(), self.g_rot.data_ptr(), self.exp_avg[0].data_ptr(),
-                              self.exp_avg_sq[0].data_ptr(), m._rot.numel(), ROT_LR, 1),
-            _lib.DgsAdamGroup(m._trans.data_ptr(), self.g_trans.data_ptr(), self.exp_avg[1].data_ptr(),
-                              self.exp_avg_sq[1].data_ptr(), m._trans.numel(), TRANS_LR, 1))
         self._peek_out = (ctypes.c_void_p * 2)(self.peek[0].data_ptr(), self.peek[1].data_ptr())
-        # ---- per group: the cameras, images, lists and gradient matrices of its K = G call
-        self.groups = [_EpochGroup(b, min(b + per_call, n)) for b in range(0, n, per_call)]
-        for g in self.groups:
-            G = g.G
-            g.view, g.full, g.campos = torch.empty((G, 4, 4), **f32), torch.empty((G, 4, 4), **f32), torch.empty((G, 3), **f32)
-            g.color, g.dcolor = torch.empty((G, 3, H, W), **f32), torch.empty((G, 3, H, W), **f32)
-            g.radii = torch.empty((G, P), dtype=torch.int32, device=dev)
-            g.drops = torch.zeros(1, dtype=torch.int32, device=dev)
-            g.g_view, g.g_proj = torch.empty((G, 4, 4), **f32), torch.empty((G, 4, 4), **f32)
-            g.host = torch.zeros(8, dtype=torch.int32).pin_memory()
-            g.geom = torch.empty(L.dgs_geom_state_bytes(P, G), dtype=torch.uint8, device=dev)
-            g.image = torch.empty(L.dgs_image_state_bytes(W, H, G), dtype=torch.uint8, device=dev)
-            g.capacity = int(capacity) if capacity is not None else self._learn_capacity(g)
-            g.binning = torch.empty(L.dgs_binning_state_bytes(g.capacity, W, H, G), dtype=torch.uint8, device=dev)
-            g.scratch = torch.empty(L.dgs_backward_scratch_bytes(g.capacity, P, G), dtype=torch.uint8, device=dev)
-            g.skip_ptr = g.geom.data_ptr() + raster_call.skip_word_offset(P, W, H, G)
-            g.prob = self._problem(g, g.binning)
-            g.out = raster_call.forward_out(g.color, None, g.radii, g.host, drop_counter=g.drops)
-            g.out_probe = raster_call.forward_out(g.color, None, g.radii, g.host)    # gradients(): skips nothing, counts nothing
-            g.io = _lib.DgsBackwardIO()
-            g.io.num_rendered = g.capacity
-            g.io.radii, g.io.dL_dout_color = _ptr(g.radii), _ptr(g.dcolor)
-            g.io.scratch, g.io.scratch_bytes = _ptr(g.scratch), g.scratch.numel()
-            g.io.dL_dviewmatrix, g.io.dL_dprojmatrix = _ptr(g.g_view), _ptr(g.g_proj)
-        self.capacity = max(g.capacity for g in self.groups)
         self._skips = (ctypes.c_void_p * len(self.groups))(*[g.skip_ptr for g in self.groups])
         self._begins = (ctypes.c_int32 * (len(self.groups) + 1))(*([g.begin for g in self.groups] + [n]))
 
-    # ------------------------------------------------------------------------------------------------ plumbing
-    def _problem(self, g, binning=None):
-        cloud, c0 = self.cloud, self.model.cams[0]
-        settings = dgr.GaussianRasterizationSettings(
-            image_height=self.H, image_width=self.W, tanfovx=math.tan(c0.FoVx * 0.5), tanfovy=math.tan(c0.FoVy * 0.5),
-            bg=self.bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
-            sh_degree=cloud.active_sh_degree, campos=g.campos, prefiltered=False, debug=False)
-        rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
-        raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
-        return raster_call.problem(g.G, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
-                                   None, g.view, g.full, g.campos, settings, self.bg, self.cull, 0, raw=raw,
-                                   geom=g.geom, image=g.image, binning=binning)
+    def _ranges(self):
+        n = self.n
+        if n > _lib.DGS_MAX_K:
+            raise NotImplementedError(f"EpochPoseFit fits at most DGS_MAX_K = {_lib.DGS_MAX_K} views (got {n}): an epoch's "
+                                      "schedule is one device block; use the sequential fit")
+        per_call = n if self._per_call is None else int(self._per_call)
+        if per_call < 1:
+            raise ValueError("views_per_call must be at least 1")
+        per_call = min(per_call, n)
+        return [(b, min(b + per_call, n)) for b in range(0, n, per_call)]
 
     def _pose_forward(self, g, rot, trans, stream):
         _lib.check(_lib.lib().dgs_testpose_forward_rows(_ptr(rot), _ptr(trans), self.n, g.begin, g.end, _ptr(self.proj),
@@ -544,13 +487,10 @@ class EpochPoseFit:
                    "dgs_testpose_forward_rows")
 
     @torch.no_grad()
-    def _learn_capacity(self, g):
-        """One exact (two-phase) K = G forward of the group at its start poses."""
-        dev = self.cloud._xyz.device
-        self._pose_forward(g, self.model._rot, self.model._trans, _stream(dev))
-        out = raster_call.forward_out(g.color, None, g.radii, g.host)
-        R, _ = raster_call.forward(dev, self._problem(g), out, g.host, None)
-        return _capacity_for(int(R))
+    def _duplicates(self, g):
+        """One exact K = G forward of the group at its start poses."""
+        self._pose_forward(g, self.model._rot, self.model._trans, _stream(self.cloud._xyz.device))
+        return g.exact_count(self)
 
     @torch.no_grad()
     def _enqueue(self, g, apply=True):
@@ -584,52 +524,22 @@ class EpochPoseFit:
     def gradients(self):
         """An epoch WITHOUT its update, enqueued eagerly, at the current parameters (every view's turn taken as the first:
         no zero-gradient step precedes it): all rows of (dL/drot [n,4], dL/dtrans [n,3]) and the views' (l1, mse) [n,2],
-        as device tensors.  (Also what loads the kernels of the chain before the capture.)"""
-        self.block.copy_(self._zero_block)
+        as device tensors."""
+        self.block.zero_()
         for g in self.groups:
             self._enqueue(g, apply=False)
         return self.g_rot.clone(), self.g_trans.clone(), self.work[:, :2].clone()
 
-    def _capture(self):
-        dev = self.cloud._xyz.device
-        self.gradients()
-        torch.cuda.synchronize(dev)
-        for g in self.groups:
-            graph = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    self._enqueue(g)
-            except RuntimeError as ex:
-                raise RuntimeError(f"the pose-fit epoch could not be captured into a hipGraph: {ex}") from ex
-            g.graph = graph
-
-    # ------------------------------------------------------------------------------------------------- the fit
     def schedule(self, orders, first_epoch=0):
         """Uploads the device schedule of a run -- one row of 5 n words per epoch (epoch_rows) -- and returns the number of
         epochs.  orders: one view order per epoch (epoch_orders); first_epoch: the StepLR epoch the first of them is."""
         if any(len(o) != self.n for o in orders):
             raise ValueError("every epoch's order must be a permutation of the views")
-        rows = epoch_rows(self.steps, orders, first_epoch, self.num_iter_per_view)
-        self._sched = torch.from_numpy(rows).to(self.block.device)
-        self._sched_pos = 0
-        if self.groups[0].graph is None:
-            self._capture()
-        return rows.shape[0]
+        return self._upload(epoch_rows(self.steps, orders, first_epoch, self.num_iter_per_view))
 
     def run(self, n_epochs=None):
-        """Enqueues the next n_epochs (default: all remaining) epochs of the uploaded schedule: per epoch one small copy
-        launch (the epoch's row into the device block) and one graph launch per group.  No host synchronisation."""
-        L = _lib.lib()
-        stream = _stream(self.cloud._xyz.device)
-        left = self._sched.shape[0] - self._sched_pos
-        n_epochs = left if n_epochs is None else min(int(n_epochs), left)
-        block = ctypes.c_void_p(self.block.data_ptr())
-        base, words = self._sched.data_ptr(), self.ROW_WORDS * self.n
-        for e in range(self._sched_pos, self._sched_pos + n_epochs):
-            _lib.check(L.dgs_copy_words(block, ctypes.c_void_p(base + 4 * words * e), words, stream), "dgs_copy_words")
-            for g in self.groups:
-                g.graph.replay()
-        self._sched_pos += n_epochs
+        """Enqueues the next n_epochs (default: all remaining) epochs of the uploaded schedule (_replay)."""
+        n_epochs = self._replay(n_epochs)
         self.steps += n_epochs * self.n
         return n_epochs
 
@@ -637,15 +547,6 @@ class EpochPoseFit:
         """View-steps skipped (a host read): a group whose K = G forward exceeded its capacity skips its rows' whole epoch,
         G view-steps -- where the sequential fit skips the one step of the view that overflowed."""
         return sum(int(g.drops.item()) * g.G for g in self.groups)
-
-    def psnr_ema(self):
-        """20 log10(1 / sqrt(l2_error_ema)) as the reference logs it (test.py:183); a host read."""
-        v = float(self.l2_ema.item())
-        return 20.0 * math.log10(1.0 / math.sqrt(v)) if v > 0.0 else float("inf")
-
-    def cameras(self):
-        with torch.no_grad():
-            return [self.model(i) for i in range(self.n)]
 
 
 def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_view=2000, order=None, seed=None,

@@ -31,7 +31,6 @@ still gets its update (the reference applies every step).
 """
 import ctypes
 import os
-import math
 
 import torch
 
@@ -329,8 +328,7 @@ class FusedStep:
         cap = self._capacity(ckey) if self.speculative else None
         if cap is None or isinstance(subframe_indice, (list, tuple)) or torch.is_tensor(subframe_indice):
             return None
-        q = 1 << max(cap.bit_length() - 5, 10)
-        cap = -(-cap // q) * q
+        cap = raster_call.round_capacity(cap)
         cull = dgr.TILE_CULL if self.tile_cull is None else bool(self.tile_cull)
         # ("subframes" sharding: the captured front ends before the backward)
         if shard is None and self._eager_is_faster(K_total, cap, cull):
@@ -571,14 +569,8 @@ class FusedStep:
         image = torch.empty(L.dgs_image_state_bytes(W, H, K), dtype=torch.uint8, device=dev)
         bg = background.to(dev, torch.float32).contiguous()
         cull = dgr.TILE_CULL if self.tile_cull is None else bool(self.tile_cull)
-        rs = dgr.GaussianRasterizationSettings(
-            image_height=H, image_width=W, tanfovx=math.tan(m.ref_cam.FoVx * 0.5), tanfovy=math.tan(m.ref_cam.FoVy * 0.5),
-            bg=bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
-            sh_degree=cloud.active_sh_degree, campos=campos, prefiltered=False, debug=False)
-        raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
-        # (compact duplicate records always: wide_records = 0)
-        prob = raster_call.problem(K, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
-                                   None, view, full, campos, rs, bg, cull, 0, raw=raw, geom=geom, image=image)
+        prob = raster_call.cloud_problem(cloud, K, view, full, campos, H, W, m.ref_cam.FoVx, m.ref_cam.FoVy, bg, cull,
+                                         geom, image)
         key = (cam, K_total, k0)
         if _cap is None:
             host = self._host_words()

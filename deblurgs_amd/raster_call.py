@@ -1,9 +1,11 @@
-"""The rasteriser's C ABI (include/dgs_hip.h) as both of its Python callers speak it -- the operator
-(diff_gaussian_rasterization) and the training step without autograd (fused_step.FusedStep): filling DgsProblem,
-DgsForwardOut and DgsBackwardIO, the two forward protocols, the meaning of the pinned count words and of the skip word,
+"""The rasteriser's C ABI (include/dgs_hip.h) as its Python callers speak it -- the operator
+(diff_gaussian_rasterization), the training step without autograd (fused_step.FusedStep) and the test-view pose fits
+(evaluation): filling DgsProblem (cloud_problem: from a GaussianCloud's raw parameters), DgsForwardOut and DgsBackwardIO,
+the two forward protocols, the meaning of the pinned count words and of the skip word, the rounding of a learnt capacity,
 and the layout of the flat gradient bucket.  Formats only: what to run when is the callers' business.
 """
 import ctypes
+import math
 from typing import NamedTuple
 
 import torch
@@ -56,6 +58,21 @@ def problem(K, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D
     return p
 
 
+def cloud_problem(cloud, K, viewmatrix, projmatrix, campos, H, W, FoVx, FoVy, bg, tile_cull, geom, image, binning=None):
+    """The DgsProblem of a K-camera call on a GaussianCloud's RAW parameters (the kernels apply the activations): compact
+    duplicate records, scale_modifier 1, nothing prefiltered, no debug; the rest coefficients only if the cloud has any."""
+    from .diff_gaussian_rasterization import GaussianRasterizationSettings      # (that module imports this one)
+    settings = GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=math.tan(FoVx * 0.5), tanfovy=math.tan(FoVy * 0.5), bg=bg,
+        scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
+        sh_degree=cloud.active_sh_degree, campos=campos, prefiltered=False, debug=False)
+    rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
+    raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
+    return problem(K, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation, None,
+                   viewmatrix, projmatrix, campos, settings, bg, tile_cull, 0, raw=raw, geom=geom, image=image,
+                   binning=binning)
+
+
 def forward_out(color, depth, radii, host, **pointers):
     """A DgsForwardOut: the images, the radii and the pinned count words (host).  `pointers` sets further fields by name
     from a tensor or a raw address: debug_contrib_checksum, or a captured step's drop_counter / status_dev /
@@ -105,6 +122,13 @@ def forward(device, prob, out, host, capacity=None):
     else:
         _lib.check(L.dgs_forward(ctypes.byref(prob), ctypes.byref(out), R, stream), "dgs_forward")
     return R, binning
+
+
+def round_capacity(cap):
+    """cap rounded up to 1/32 of its leading power of two (at least 1024): steps of 3-6 %, so that small drifts of a
+    duplicate count do not change the capacity -- and with it the size of every list and what a captured graph holds."""
+    q = 1 << max(cap.bit_length() - 5, 10)
+    return -(-cap // q) * q
 
 
 def skip_word_offset(P, W, H, K):

@@ -168,3 +168,62 @@ def test_epoch_fit_refuses_a_cpu_cloud():
         ev.EpochPoseFit(Cloud(), [], [], torch.zeros(3), "identity")
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ev.FusedPoseFit(Cloud(), [], [], torch.zeros(3), "identity")
+
+
+class _StandInCloud:
+    """The attributes of a GaussianCloud that raster_call.cloud_problem reads, as CPU tensors (P = 4)."""
+
+    def __init__(self, n_rest, isotropic):
+        g = torch.Generator().manual_seed(3)
+        P = 4
+        self._xyz = torch.randn(P, 3, generator=g)
+        self._features_dc = torch.randn(P, 1, 3, generator=g)
+        self._features_rest = torch.randn(P, n_rest, 3, generator=g)
+        self._opacity = torch.randn(P, 1, generator=g)
+        self._scaling = torch.randn(P, 3, generator=g)
+        self._rotation = torch.randn(P, 4, generator=g)
+        self.active_sh_degree, self.scale_lower_bound, self.use_isotrophic = 2, 0.003, isotropic
+        self.z_near, self.z_far, self.use_sigmoid = 0.2, 100.0, True
+
+
+@pytest.mark.parametrize("n_rest, isotropic", [(8, True), (0, False)])
+def test_cloud_problem_equals_the_spelled_out_problem(n_rest, isotropic):
+    """raster_call.cloud_problem against raster_call.problem called with the settings, the raw dict and the fixed
+    arguments written out (dgs_context_create allocates nothing on a device, so CPU tensors fill a DgsProblem): the two
+    structs byte for byte; a cloud without rest coefficients sends a null shs_rest and M = 1."""
+    import math
+    from deblurgs_amd import raster_call
+    from deblurgs_amd import diff_gaussian_rasterization as dgr
+    K, H, W, FoVx, FoVy, cull = 2, 24, 40, 0.9, 0.6, True
+    cloud = _StandInCloud(n_rest, isotropic)
+    view, full, campos = torch.rand(K, 4, 4), torch.rand(K, 4, 4), torch.rand(K, 3)
+    bg = torch.tensor([0.2, 0.3, 0.1])
+    geom, image, binning = (torch.zeros(64, dtype=torch.uint8), torch.zeros(96, dtype=torch.uint8),
+                            torch.zeros(128, dtype=torch.uint8))
+    rs = dgr.GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=math.tan(FoVx * 0.5), tanfovy=math.tan(FoVy * 0.5),
+        bg=bg, scale_modifier=1.0, z_near=cloud.z_near, z_far=cloud.z_far, use_sigmoid=cloud.use_sigmoid,
+        sh_degree=cloud.active_sh_degree, campos=campos, prefiltered=False, debug=False)
+    rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
+    raw = {"scale_lb": cloud.scale_lower_bound, "sh_rest": rest, "isotropic": getattr(cloud, "use_isotrophic", False)}
+    for blob in (None, binning):
+        want = raster_call.problem(K, cloud._xyz, cloud._features_dc, None, cloud._opacity, cloud._scaling, cloud._rotation,
+                                   None, view, full, campos, rs, bg, cull, 0, raw=raw, geom=geom, image=image, binning=blob)
+        got = raster_call.cloud_problem(cloud, K, view, full, campos, H, W, FoVx, FoVy, bg, cull, geom, image, blob)
+        assert bytes(got) == bytes(want)
+        assert got.P == 4 and got.K == K and got.D == 2 and got.wide_records == 0 and got.geom_state == geom.data_ptr()
+        assert got.raw_params == (3 if isotropic else 1) and got.scale_lb == pytest.approx(0.003, rel=1e-6)
+        assert got.binning_state == (None if blob is None else binning.data_ptr())
+    if n_rest == 0:
+        assert not got.shs_rest and got.M == 1
+    else:
+        assert got.shs_rest == cloud._features_rest.data_ptr() and got.M == 9
+
+
+def test_round_capacity_on_pinned_values():
+    """1/32 of the leading power of two, at least 1024 (by hand: 166384 has 18 bits, q = 8192, 21 q = 172032; 1000000 has
+    20 bits, q = 32768, 31 q = 1015808); the fits' capacity for a need of 100000 is round(100000 + 50000 + 16384)."""
+    from deblurgs_amd import evaluation as ev, raster_call
+    for cap, want in ((1, 1024), (16384, 16384), (166384, 172032), (1000000, 1015808)):
+        assert raster_call.round_capacity(cap) == want, cap
+    assert ev._capacity_for(100000) == 172032
