@@ -201,6 +201,12 @@ EXPORTS = {
     "dgs_image_metrics_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "dgs_image_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dgs_frames_finish": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_float] * 2 +
+                          [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2),
+    "dgs_depth_range_tmp_bytes": (ctypes.c_size_t, [ctypes.c_uint64]),
+    "dgs_depth_range": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 3),
+    "dgs_depth_colorize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_float, ctypes.c_float] +
+                           [ctypes.c_void_p] * 3),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

@@ -31,6 +31,8 @@ SOURCES = {
     "loss.hip": [],
     # SSIM of identical images is exactly 1 only while 2 mu1 mu2 and mu1^2 + mu2^2 round the same way
     "metrics.hip": ["-ffp-contract=off"],
+    # the 8-bit frames restate numpy's clip * 255 -> astype(uint8) one rounding per statement
+    "frames.hip": ["-ffp-contract=off"],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -580,12 +580,38 @@ def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_vi
 
 
 @torch.no_grad()
-def evaluate(cams, cloud, bg, gt_images, tone_mapping):
+def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call):
+    """evaluate() with the cameras rendered views_per_call at a time: one K-fused forward-only call per group
+    (render_path.render_group), then the per-view metrics of evaluate() on slot k, summed in the same order."""
+    from . import render_path
+    cams = list(cams)
+    psnr_test, ssim_test = 0.0, 0.0
+    for b, e in render_path.frame_groups(cams, views_per_call):
+        images = render_path.render_group(cams[b:e], cloud, bg)["render"]
+        for k in range(e - b):
+            image = tone_mapping(images[k]).contiguous()
+            gt = gt_images[b + k].to(image)
+            if image.device.type == "cuda":
+                both = metrics.psnr_ssim(image, gt.contiguous())
+                psnr_test += both[2:5].reshape(3, 1).mean().item()
+                ssim_test += both[1].mean().item()
+            else:
+                psnr_test += metrics.psnr(image, gt).mean().item()
+                ssim_test += metrics.ssim(image, gt).mean().item()
+    return psnr_test / len(cams), ssim_test / len(cams)
+
+
+@torch.no_grad()
+def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None):
     """test.py:93-129 without LPIPS: (mean PSNR, mean SSIM) over the cameras.  The render of every camera goes through the
     forward_only inference path (gaussian_renderer.render under no_grad), is tone-mapped and NOT clamped, and both metrics
-    come from one fused kernel per view (metrics.psnr / metrics.ssim)."""
+    come from one fused kernel per view (metrics.psnr / metrics.ssim).
+    views_per_call: None renders one camera per call; a number renders the cameras that many at a time through the
+    K-fused forward-only call -- slot i of such a call is the K = 1 render bit for bit, so the two floats are the same."""
     if tone_mapping is None or isinstance(tone_mapping, str):
         tone_mapping = losses.ToneMapping(tone_mapping or "identity")
+    if views_per_call is not None:
+        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call)
     psnr_test, ssim_test = 0.0, 0.0
     n = len(cams)
     for cam, gt in zip(cams, gt_images):

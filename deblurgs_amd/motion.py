@@ -170,6 +170,18 @@ class CameraMotionModule:
         return [MiniCam(r.image_width, r.image_height, r.FoVy, r.FoVx, r.znear, r.zfar, wv[i], fp[i], cc[i])
                 for i in range(wv.shape[0])]
 
+    @torch.no_grad()
+    def get_middle_cams(self):
+        """scene/motion.py:322-334: per training image the camera at the middle sample of its nu (index f // 2 of the f
+        sorted samples) -- the sharp view a blurry image is drawn around; what render_trainview and the spiral path start
+        from.  (With curve_random_sample on, every call draws its jitter, as the reference's does.)"""
+        cams = []
+        for i in range(len(self)):
+            nu = self._sample_nu_from_alignment(i)
+            mid = nu.shape[0] // 2
+            cams.append(self.get_trajectory(i, nu[mid:mid + 1])[0])
+        return cams
+
     def get_gt_image(self, idx):
         return self.gt_images[idx]
 

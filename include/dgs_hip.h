@@ -597,6 +597,29 @@ int dgs_l2_ema_epoch(const float* work, const int32_t* pos, int32_t n, const uin
 size_t dgs_image_metrics_tmp_bytes(int32_t W, int32_t H);
 int dgs_image_metrics(const float* a, const float* b, int32_t W, int32_t H, void* tmp, float* out, dgs_stream_t stream);
 
+/* ---- camera-path frames (additions to ABI 15; render_spiral.py:27-35, render_trainview.py:33-52 of the reference) ----
+ * K rendered frames color [K,3,H,W] (fp32, the rasteriser's output) -> packed 8-bit frames out [K,h,w,3] of the window
+ * rows [y0, y0 + h) x columns [x0, x0 + w), in one pass:  y = tone_map(x) (DGS_TONE_*, the expression and the powf of
+ * dgs_view_loss_grad), then (uint8)(min(max(y, 0), 1) * 255.0f) -- numpy's (y.clip(0, 1) * 255.0).astype(uint8), whose cast
+ * truncates.  A NaN input writes 0 (numpy leaves that cast undefined).  `out` needs no alignment.  Errors: K < 1 (or above
+ * 65535), an empty window or one that leaves the image (or is taller than 65535 rows), a tone id that is neither,
+ * bound >= 0.5 with DGS_TONE_GAMMA. */
+int dgs_frames_finish(const float* color, int32_t K, int32_t H, int32_t W, int32_t tone_mapping, float eps, float bound,
+                      int32_t y0, int32_t x0, int32_t h, int32_t w, uint8_t* out, dgs_stream_t stream);
+/* lo_hi[0] = min, lo_hi[1] = max of n floats, left in device memory: per-block fminf / fmaxf, then one block over the
+ * blocks' results -- two launches, a block count that depends on n only.  NaNs do not count (torch.min / torch.max return
+ * NaN when one is present; the rasteriser's depth holds none); n NaNs leave (+inf, -inf).
+ * tmp >= dgs_depth_range_tmp_bytes(n), 4-byte aligned. */
+size_t dgs_depth_range_tmp_bytes(uint64_t n);
+int dgs_depth_range(const float* depth, uint64_t n, float* lo_hi, void* tmp, dgs_stream_t stream);
+/* depth_colorize (utils/export_utils.py:44-65) with its default clip_percentage = 1, the range read from the two device
+ * words dgs_depth_range left:  lo = max(z_near, lo_hi[0]), hi = min(z_far, lo_hi[1]), d = clip((x - lo) / (hi - lo), 0, 1),
+ * out[e] = lut[min((int)(d * 256), 255)] -- the colour map's own indexing of a float in [0, 1].  lut [256,4] and out [n,4]
+ * are RGBA bytes, both 4-byte aligned; the table holds (colour * 255) truncated.  hi == lo or a NaN writes (0, 0, 0, 0), the
+ * colour the map gives a value it cannot place. */
+int dgs_depth_colorize(const float* depth, uint64_t n, const float* lo_hi, float z_near, float z_far, const uint8_t* lut,
+                       uint8_t* out, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
