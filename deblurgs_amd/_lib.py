@@ -207,6 +207,14 @@ EXPORTS = {
     "dgs_depth_range": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 3),
     "dgs_depth_colorize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_float, ctypes.c_float] +
                            [ctypes.c_void_p] * 3),
+    "dgs_order_stats_tmp_bytes": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_int32]),
+    "dgs_order_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32] +
+                        [ctypes.c_void_p] * 3),
+    "dgs_percentiles": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double), ctypes.c_int32] +
+                        [ctypes.c_void_p] * 3),
+    "dgs_report_images": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 5 + [ctypes.c_float] * 2 +
+                          [ctypes.c_void_p] * 5),
+    "dgs_scalar_colorize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

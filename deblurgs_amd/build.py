@@ -33,6 +33,8 @@ SOURCES = {
     "metrics.hip": ["-ffp-contract=off"],
     # the 8-bit frames restate numpy's clip * 255 -> astype(uint8) one rounding per statement
     "frames.hip": ["-ffp-contract=off"],
+    # report images, percentiles and colours restate torch / numpy expressions one rounding per statement
+    "report.hip": ["-ffp-contract=off"],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -579,8 +579,15 @@ def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_vi
     return fit.cameras()
 
 
+def _write_view(vis_dir, i, image, gt, writer):
+    """The three files of view i (test.py:122-126) from the image the metrics were taken of."""
+    if vis_dir is not None:
+        from . import report
+        report.write_view_report(vis_dir, i, image, gt.contiguous(), writer)
+
+
 @torch.no_grad()
-def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call):
+def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir=None, writer=None):
     """evaluate() with the cameras rendered views_per_call at a time: one K-fused forward-only call per group
     (render_path.render_group), then the per-view metrics of evaluate() on slot k, summed in the same order."""
     from . import render_path
@@ -591,6 +598,7 @@ def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call):
         for k in range(e - b):
             image = tone_mapping(images[k]).contiguous()
             gt = gt_images[b + k].to(image)
+            _write_view(vis_dir, b + k, image, gt, writer)
             if image.device.type == "cuda":
                 both = metrics.psnr_ssim(image, gt.contiguous())
                 psnr_test += both[2:5].reshape(3, 1).mean().item()
@@ -602,21 +610,31 @@ def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call):
 
 
 @torch.no_grad()
-def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None):
+def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_dir=None, writer=None):
     """test.py:93-129 without LPIPS: (mean PSNR, mean SSIM) over the cameras.  The render of every camera goes through the
     forward_only inference path (gaussian_renderer.render under no_grad), is tone-mapped and NOT clamped, and both metrics
     come from one fused kernel per view (metrics.psnr / metrics.ssim).
     views_per_call: None renders one camera per call; a number renders the cameras that many at a time through the
-    K-fused forward-only call -- slot i of such a call is the K = 1 render bit for bit, so the two floats are the same."""
+    K-fused forward-only call -- slot i of such a call is the K = 1 render bit for bit, so the two floats are the same.
+    vis_dir: a directory (removed and recreated, as test.py:104-107 prepares model_path/vis_dir) that receives
+    III_gt.png, III_render.png and III_error.png -- the jet-coloured L1 map -- per view (report.write_view_report: the
+    images are made on the device, needs a HIP device); writer(path, array) takes the place of the files (then no
+    directory is touched).  The two floats, and the files, do not depend on views_per_call; the floats not on vis_dir."""
     if tone_mapping is None or isinstance(tone_mapping, str):
         tone_mapping = losses.ToneMapping(tone_mapping or "identity")
+    if writer is not None and vis_dir is None:
+        raise ValueError("writer takes the place of the files under vis_dir: give vis_dir too (it names the paths)")
+    if vis_dir is not None and writer is None:
+        from . import report
+        report.fresh_directory(vis_dir)
     if views_per_call is not None:
-        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call)
+        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir, writer)
     psnr_test, ssim_test = 0.0, 0.0
     n = len(cams)
-    for cam, gt in zip(cams, gt_images):
+    for i, (cam, gt) in enumerate(zip(cams, gt_images)):
         image = tone_mapping(gaussian_renderer.render(cam, cloud, bg)["render"]).contiguous()
         gt = gt.to(image)
+        _write_view(vis_dir, i, image, gt, writer)
         if image.device.type == "cuda":       # one launch for both: the values metrics.psnr / metrics.ssim return
             both = metrics.psnr_ssim(image, gt.contiguous())
             psnr_test += both[2:5].reshape(3, 1).mean().item()

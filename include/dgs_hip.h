@@ -620,6 +620,42 @@ int dgs_depth_range(const float* depth, uint64_t n, float* lo_hi, void* tmp, dgs
 int dgs_depth_colorize(const float* depth, uint64_t n, const float* lo_hi, float z_near, float z_far, const uint8_t* lut,
                        uint8_t* out, dgs_stream_t stream);
 
+/* ---- visual reports (additions to ABI 15; test.py:122-126, utils/visualization.py:262-291, utils/colorize.py:63-107 of
+ * the reference) ----  Raw device pointers and a stream, nothing kept between calls, no global or float atomics, no
+ * device word read by the host; every argument is checked before the first HIP call.
+ *
+ * Exact order statistics by radix select: out[j] = the element np.sort(x)[ranks[j]] holds, x float32 [n], 1 <= n <= 2^32 - 1,
+ * 1 <= m <= 4 host ranks below n.  Four most-significant-first 8-bit passes over the order-preserving key (sign set: ~bits;
+ * else bits | 0x80000000; a NaN: 0xFFFFFFFF, so NaNs come last as numpy sorts them; a returned NaN is the quiet positive
+ * one); one data pass serves all m ranks.  -0.0 sorts before +0.0 (numpy holds them equal: either may stand at a rank).
+ * tmp >= dgs_order_stats_tmp_bytes(n, m) bytes, 4-byte aligned: a function of n and m only (it serves dgs_percentiles
+ * with the same n and m too). */
+size_t dgs_order_stats_tmp_bytes(uint64_t n, int32_t m);
+int dgs_order_stats(const float* x, uint64_t n, const uint64_t* ranks_host, int32_t m, float* out, void* tmp,
+                    dgs_stream_t stream);
+/* numpy's np.percentile(x, q_tuple) (method "linear", float32 x, float64 results) for 1 <= m <= 4 percentages in
+ * [0, 100]: the host forms v = (n - 1) (q / 100) in double, i = floor(v), g = v - i (from v = n - 1 on: i = i + 1 = n - 1
+ * and g = v + 1, as numpy forms them there); the device selects a = x_(i) and b = x_(i + 1) (one select of 2 m ranks),
+ * d = (float)(b - a), out[j] = (double)a + (double)d g, or (double)b - (double)d (1 - g) when g >= 0.5.
+ * out: m float64 device words, 8-byte aligned. */
+int dgs_percentiles(const float* x, uint64_t n, const double* q_host, int32_t m, double* out, void* tmp,
+                    dgs_stream_t stream);
+/* The 8-bit images and the L1 error map of a report in one pass.  x [K,3,H,W] linear renders.  mean = 1: ONE image
+ * y = tone_map(s), s = (((x_0 + x_1) + ...) + x_{K-1}) / (float)K summed in order in fp32, gt [3,H,W]; mean = 0: K images
+ * y_k = tone_map(x_k), gt [K,3,H,W] (G = 1 or K images leave).  tone_map: DGS_TONE_*, dgs_frames_finish's expression (a
+ * NaN input stays NaN).  out_u8 [G,H,W,3] = (uint8)clamp(y * 255 + 0.5, 0, 255), torchvision's save_image rounding, a NaN
+ * gives 0; gt_u8 [G,H,W,3] (or NULL) the same of gt itself; err [G,H,W] (or NULL) = ((|gt_r - y_r| + |gt_g - y_g|) +
+ * |gt_b - y_b|) / 3.0f with y unclamped: torch.abs(gt - image).permute(1, 2, 0).mean(-1).  gt may be NULL (then gt_u8 and
+ * err must be): subframes.  No pointer needs more than its type's alignment. */
+int dgs_report_images(const float* x, int32_t K, int32_t mean, int32_t H, int32_t W, int32_t tone_mapping, float eps,
+                      float bound, const float* gt, uint8_t* out_u8, uint8_t* gt_u8, float* err, dgs_stream_t stream);
+/* colorize_np (utils/colorize.py:87-92) once the range is known: lo_hi two float64 device words (8-byte aligned),
+ * c = min(max((double)x, lo), hi), d = (c - lo) / (hi - lo), out[e] = the first three bytes of lut[min((int)(d * 256), 255)]
+ * -- float64 throughout, as numpy 2 promotes a float32 array against float64 scalars.  lut [256,4] RGBA bytes, 4-byte
+ * aligned; out [n,3] bytes, any alignment.  hi == lo or a NaN in the chain writes (0, 0, 0). */
+int dgs_scalar_colorize(const float* x, uint64_t n, const double* lo_hi, const uint8_t* lut, uint8_t* out,
+                        dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
