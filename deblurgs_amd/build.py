@@ -35,6 +35,9 @@ SOURCES = {
     "frames.hip": ["-ffp-contract=off"],
     # report images, percentiles and colours restate torch / numpy expressions one rounding per statement
     "report.hip": ["-ffp-contract=off"],
+    # LPIPS: the convolution's compensated (Kahan) sum must not be contracted across its statements; the z-score and the
+    # layer distance round once per statement, as the torch expressions do (the MFMA chains are builtins: unaffected)
+    "lpips.hip": ["-ffp-contract=off"],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -1,0 +1,460 @@
+// lpips.hip -- LPIPS with the AlexNet backbone, the third number of the reference's evaluation (test.py:120,
+// lpipsPyTorch/modules/{lpips,networks,utils}.py), with caller-supplied weights:
+//   * conv_kernel: ONE implicit-GEMM fp32 convolution for all five layers on the f32-input matrix cores
+//     (v_mfma_f32_32x32x2_f32), with bias + ReLU in the epilogue and the z-score of the input fused into the first
+//     layer's gather;
+//   * maxpool_kernel: 3 x 3 stride 2, floor, no padding;
+//   * layer_distance_kernel + lpips_finish_kernel: per tap the channel-normalised squared difference under the "lin"
+//     weights, reduced over space in block order.
+// Built with -ffp-contract=off (deblurgs_amd/build.py): the compensated sum of the convolution below is only what it says
+// while the compiler forms no FMA across its statements, and (x - mean) / std and the distance's sums round once per
+// statement, as the torch expressions do.
+//
+// The arithmetic of an output element never depends on where its image stands in the call: every element is the same
+// k-ordered chain whatever block, wave or lane holds it, every spatial sum is cut into blocks by the image size alone.
+// So a pair's six numbers are bitwise those of a call on that pair alone, lpips(x, x) is exactly 0 and
+// lpips(x, y) == lpips(y, x) ((a - b)^2 == (b - a)^2).  No float atomics anywhere.
+#include <math.h>
+
+#include "dgs_common.h"
+
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int LP_BK = 32;         // k per LDS tile, and per accumulator chain (see conv_kernel)
+constexpr int LP_BN = 128;        // output pixels per block
+constexpr int LP_MIN = 31;        // smallest image: conv1 7 x 7, pool 3 x 3, conv2 3 x 3, pool 1 x 1
+
+struct ConvArgs {
+  const float* in0;     // images [0, n_half) [n_half,Cin,IH,IW]
+  const float* in1;     // images [n_half, n_img)
+  int n_half;
+  const float* w;       // [Cout, K] row-major, K = Cin KH KW in (ci, ky, kx) order: the weight tensor as it is
+  const float* bias;    // [Cout]
+  float* out;           // [n_img, Cout, OH, OW]
+  int Cin, IH, IW, Cout, OH, OW, KH, KW, stride, pad, K, N;   // N = n_img OH OW
+};
+
+// C[Cout x N] = W[Cout x K] . patches[K x N]: a block computes a (WM TM 32) x 128 tile of C with four waves, wave
+// (wm, wn) a TM x TN grid of 32 x 32 MFMA tiles.  Per 32 k: the W tile goes to LDS transposed (s_a[k][m]), the patch
+// values are gathered on the fly into s_b[k][n] (0 where the window leaves the image or k, n pass their ends), then
+// 16 k-steps of v_mfma_f32_32x32x2_f32 -- lane l feeds A[m = l & 31][k = l >> 5] and B[k = l >> 5][n = l & 31], one
+// ds_read_b32 each, 32 consecutive floats per lane group: conflict-free.
+// Numerics: the MFMA is an exact k-ordered fmaf chain.  One chain over all of K (up to 3456 terms) drifts by several
+// ulp, which the thin last taps of a small image show (one pixel, 256 channels: no averaging); so every 32-k tile starts
+// a fresh chain from 0 and the tiles' partial sums are added with a compensated (Kahan) fp32 sum -- four VALU operations
+// per accumulator register and tile, next to 16 MFMAs.  Everything stays fp32.
+// (k -> (ci, ky, kx) costs two integer divisions: the first 32 threads do them once per tile, two tiles ahead, into a
+// double-buffered LDS table.)
+template <int WM, int WN, int TM, int TN, bool ZSCORE>
+__global__ void __launch_bounds__(256) conv_kernel(const ConvArgs g) {
+  constexpr int BM = WM * TM * 32;
+  static_assert(WM * WN == 4 && WN * TN * 32 == LP_BN, "four waves, 128 pixels");
+  __shared__ float s_a[LP_BK][BM + 1];
+  __shared__ float s_b[LP_BK][LP_BN];
+  __shared__ int s_koff[2][LP_BK], s_kinfo[2][LP_BK];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * LP_BN;
+  const int ohw = g.OH * g.OW, khw = g.KH * g.KW, ihw = g.IH * g.IW;
+
+  // the output pixel whose patches this thread gathers
+  const int n_mine = n0 + (t & (LP_BN - 1));
+  const bool n_ok = n_mine < g.N;
+  int img = 0, iy0 = 0, ix0 = 0;
+  if (n_ok) {
+    img = n_mine / ohw;
+    const int p = n_mine - img * ohw;
+    const int oy = p / g.OW;
+    iy0 = oy * g.stride - g.pad;
+    ix0 = (p - oy * g.OW) * g.stride - g.pad;
+  }
+  const float* src = (img < g.n_half) ? g.in0 + (size_t)img * g.Cin * ihw : g.in1 + (size_t)(img - g.n_half) * g.Cin * ihw;
+  const int pix0 = iy0 * g.IW + ix0;
+
+  auto fill_table = [&](int kt, int b) {
+    if (t < LP_BK) {
+      const int k = kt * LP_BK + t;
+      int off = 0, info = -1;
+      if (k < g.K) {
+        const int ci = k / khw, r = k - ci * khw;
+        const int ky = r / g.KW, kx = r - ky * g.KW;
+        off = ci * ihw + ky * g.IW + kx;
+        info = (ci << 8) | (ky << 4) | kx;
+      }
+      s_koff[b][t] = off;
+      s_kinfo[b][t] = info;
+    }
+  };
+
+  f32x16 tot[TM][TN], comp[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        tot[i][j][r] = 0.0f;
+        comp[i][j][r] = 0.0f;
+      }
+
+  // Software pipeline: the global loads of tile kt + 1 are issued into registers before the MFMAs of tile kt and stored to
+  // LDS after them, so their latency hides behind the matrix work (without it the gather, two loads in flight per
+  // thread, took five times the MFMA time).  The k table of a tile is written two tiles ahead of its use.
+  float ra[BM / 8], rb[LP_BK / 2];
+  unsigned zs_ci = 0;   // ZSCORE: 2 bits per staged patch value: 0 = not from the image (stays 0), else channel + 1
+  auto load_tile = [&](int kt) {
+    const int b = kt & 1;
+    const int k = kt * LP_BK + (t & 31);   // W tile: 32 consecutive k of one row per lane group
+#pragma unroll
+    for (int i = 0; i < BM / 8; i++) {
+      const int m = m0 + (t >> 5) + 8 * i;
+      ra[i] = (m < g.Cout && k < g.K) ? g.w[(size_t)m * g.K + k] : 0.0f;
+    }
+    zs_ci = 0;
+#pragma unroll
+    for (int i = 0; i < LP_BK / 2; i++) {  // patch tile: this thread's pixel at 16 of the 32 k
+      const int k_l = (t >> 7) + 2 * i;
+      const int info = s_kinfo[b][k_l], off = s_koff[b][k_l];
+      const int iy = iy0 + ((info >> 4) & 15), ix = ix0 + (info & 15);
+      const bool in = n_ok && info >= 0 && (unsigned)iy < (unsigned)g.IH && (unsigned)ix < (unsigned)g.IW;
+      rb[i] = in ? src[off + pix0] : 0.0f;
+      if (ZSCORE && in) zs_ci |= (unsigned)((info >> 8) + 1) << (2 * i);
+    }
+  };
+  auto store_tile = [&]() {
+#pragma unroll
+    for (int i = 0; i < BM / 8; i++) s_a[t & 31][(t >> 5) + 8 * i] = ra[i];
+#pragma unroll
+    for (int i = 0; i < LP_BK / 2; i++) {
+      float v = rb[i];
+      if (ZSCORE) {  // networks.py:41-51; a value from outside the image stays 0: the padding pads the z-scored image
+        const unsigned c = (zs_ci >> (2 * i)) & 3u;
+        const float mean = c == 1 ? -.030f : (c == 2 ? -.088f : -.188f);
+        const float sd = c == 1 ? .458f : (c == 2 ? .448f : .450f);
+        v = (c != 0) ? (v - mean) / sd : 0.0f;
+      }
+      s_b[(t >> 7) + 2 * i][t & (LP_BN - 1)] = v;
+    }
+  };
+
+  const int n_kt = (g.K + LP_BK - 1) / LP_BK;
+  fill_table(0, 0);
+  __syncthreads();
+  load_tile(0);
+  if (n_kt > 1) fill_table(1, 1);
+  for (int kt = 0; kt < n_kt; kt++) {
+    store_tile();
+    __syncthreads();
+    if (kt + 1 < n_kt) load_tile(kt + 1);
+    if (kt + 2 < n_kt) fill_table(kt + 2, kt & 1);
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int j = 0; j < TN; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+#pragma unroll
+    for (int kk = 0; kk < LP_BK; kk += 2) {
+      const int kr = kk + (lane >> 5);
+      float a[TM], bv[TN];
+#pragma unroll
+      for (int i = 0; i < TM; i++) a[i] = s_a[kr][(wm * TM + i) * 32 + (lane & 31)];
+#pragma unroll
+      for (int j = 0; j < TN; j++) bv[j] = s_b[kr][(wn * TN + j) * 32 + (lane & 31)];
+#pragma unroll
+      for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < TN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bv[j], acc[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int j = 0; j < TN; j++) {  // Kahan: tot += acc with the rounding error of the addition carried in comp
+        const f32x16 y = acc[i][j] - comp[i][j];
+        const f32x16 s = tot[i][j] + y;
+        comp[i][j] = (s - tot[i][j]) - y;
+        tot[i][j] = s;
+      }
+    __syncthreads();
+  }
+
+  // bias + ReLU (a NaN passes, as torch's relu passes it).  C/D layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) +
+  // 4 (lane >> 5): per register the 32 lanes of a group write 32 consecutive pixels of one channel.
+#pragma unroll
+  for (int j = 0; j < TN; j++) {
+    const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
+    if (n >= g.N) continue;
+    const int im = n / ohw, p = n - im * ohw;
+    float* dst = g.out + (size_t)im * g.Cout * ohw + p;
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (m < g.Cout) {
+          const float v = tot[i][j][r] + g.bias[m];
+          dst[(size_t)m * ohw] = (v < 0.0f) ? 0.0f : v;
+        }
+      }
+  }
+}
+
+// max_pool2d(kernel 3, stride 2): out[i][y][x] = max over in[i][2y .. 2y + 2][2x .. 2x + 2], planes = n_img C.  Every window
+// lies inside the image (floor, no padding); a NaN in the window is the result, as torch gives it.
+__global__ void __launch_bounds__(256)
+maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, size_t planes, int IH, int IW, int PH, int PW) {
+  const size_t total = planes * (size_t)PH * (size_t)PW;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t plane = e / ((size_t)PH * PW);
+    const int p = (int)(e - plane * ((size_t)PH * PW));
+    const int y = p / PW, x = p - y * PW;
+    const float* s = in + plane * (size_t)IH * IW + (size_t)(2 * y) * IW + 2 * x;
+    float m = s[0];
+#pragma unroll
+    for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+      for (int dx = 0; dx < 3; dx++) {
+        const float v = s[dy * IW + dx];
+        m = (v > m || v != v) ? v : m;
+      }
+    out[e] = m;
+  }
+}
+
+// sum over the 256 threads of a block in a fixed order (as metrics.hip's); valid in thread 0
+__device__ __forceinline__ double lp_block_sum_256(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// One tap of one pair (blockIdx.y): f [2 n_pairs, C, HW], image `pair` against image n_pairs + pair.  A thread per pixel:
+// na = sqrt(sum_c a_c^2) + 1e-10 and nb alike (utils.py:6-8), then sum_c lin_c (a_c / na - b_c / nb)^2, channels in
+// order, fp32; the block adds its 256 pixels in a fixed tree and writes partials[pair][block].
+__global__ void __launch_bounds__(256)
+layer_distance_kernel(const float* __restrict__ f, int n_pairs, int C, int HW, const float* __restrict__ lin,
+                      double* __restrict__ partials) {
+  __shared__ double red[256];
+  const int pair = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const float* a = f + (size_t)pair * C * HW;
+  const float* b = f + (size_t)(n_pairs + pair) * C * HW;
+  float s = 0.0f;
+  if (p < HW) {
+    float sa = 0.0f, sb = 0.0f;
+    for (int c = 0; c < C; c++) {
+      const float va = a[(size_t)c * HW + p], vb = b[(size_t)c * HW + p];
+      sa += va * va;
+      sb += vb * vb;
+    }
+    const float na = sqrtf(sa) + 1e-10f, nb = sqrtf(sb) + 1e-10f;
+    for (int c = 0; c < C; c++) {
+      const float d = a[(size_t)c * HW + p] / na - b[(size_t)c * HW + p] / nb;
+      s += lin[c] * (d * d);
+    }
+  }
+  const double tot = lp_block_sum_256((double)s, red);
+  if (threadIdx.x == 0) partials[(size_t)pair * gridDim.x + blockIdx.x] = tot;
+}
+
+struct LpipsTaps {
+  size_t first[5];   // where a tap's partials start (in doubles); pair i's blocks at first + i * blocks
+  int blocks[5];
+  double hw[5];
+};
+
+// One block per pair: per tap the blocks' sums in index order / HW; out[pair] = (total, layer 1..5)
+__global__ void __launch_bounds__(256) lpips_finish_kernel(const double* __restrict__ partials, LpipsTaps taps, float* __restrict__ out) {
+  __shared__ double red[256];
+  const int pair = blockIdx.x;
+  double total = 0.0;
+  for (int l = 0; l < 5; l++) {
+    const double* src = partials + taps.first[l] + (size_t)pair * taps.blocks[l];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < taps.blocks[l]; i += 256) s += src[i];
+    s = lp_block_sum_256(s, red);
+    const double mean = s / taps.hw[l];
+    total += mean;
+    if (threadIdx.x == 0) out[6 * (size_t)pair + 1 + l] = (float)mean;
+  }
+  if (threadIdx.x == 0) out[6 * (size_t)pair] = (float)total;
+}
+
+// ---- host side
+struct ConvShape {
+  int Cout, Cin, k, stride, pad, pool;
+};
+const ConvShape LP_CONVS[5] = {{64, 3, 11, 4, 2, 1}, {192, 64, 5, 1, 2, 1}, {384, 192, 3, 1, 1, 0},
+                               {256, 384, 3, 1, 1, 0}, {256, 256, 3, 1, 1, 0}};
+
+struct LpipsPlan {
+  int oh[5], ow[5];   // the taps' sizes
+  int ph[2], pw[2];   // the two pooled sizes
+  size_t buf_a, buf_b;  // floats: buf_a holds taps 1, 2, 3, 5, buf_b the two pooled maps and tap 4
+  size_t off_b, off_partials, total_bytes;
+  LpipsTaps taps;
+};
+
+size_t lp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// false: an image below 31 x 31, no pairs, or sizes this launch arithmetic does not cover
+bool lpips_plan(int W, int H, int n_pairs, LpipsPlan& P) {
+  if (W < LP_MIN || H < LP_MIN || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
+  int h = H, w = W, np = 0;
+  const size_t n_img = 2 * (size_t)n_pairs;
+  size_t a = 0, b = 0, partial = 0;
+  for (int l = 0; l < 5; l++) {
+    const ConvShape& c = LP_CONVS[l];
+    h = (h + 2 * c.pad - c.k) / c.stride + 1;
+    w = (w + 2 * c.pad - c.k) / c.stride + 1;
+    P.oh[l] = h;
+    P.ow[l] = w;
+    const size_t tap = n_img * c.Cout * (size_t)h * w;
+    if (l == 3) b = tap > b ? tap : b; else a = tap > a ? tap : a;
+    P.taps.first[l] = partial;
+    P.taps.blocks[l] = (h * w + 255) / 256;
+    P.taps.hw[l] = (double)h * (double)w;
+    partial += (size_t)n_pairs * P.taps.blocks[l];
+    if (c.pool) {
+      h = (h - 3) / 2 + 1;
+      w = (w - 3) / 2 + 1;
+      P.ph[np] = h;
+      P.pw[np] = w;
+      np++;
+      const size_t pooled = n_img * c.Cout * (size_t)h * w;
+      b = pooled > b ? pooled : b;
+    }
+  }
+  // (int32 arithmetic of the kernels: pixels of a call, elements of one image's feature map)
+  if (n_img * (size_t)P.oh[0] * P.ow[0] >= ((size_t)1 << 31) || (size_t)3 * H * W >= ((size_t)1 << 31)) return false;
+  P.buf_a = a;
+  P.buf_b = b;
+  P.off_b = lp_align(a * sizeof(float));
+  P.off_partials = P.off_b + lp_align(b * sizeof(float));
+  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
+  return true;
+}
+
+hipError_t launch_conv(const ConvArgs& g, bool zscore, hipStream_t s) {
+  const unsigned gx = (unsigned)((g.N + LP_BN - 1) / LP_BN);
+  if (g.Cout <= 64) {  // 64 x 128 tiles: wave w takes pixels 32 w .. 32 w + 31
+    const dim3 grid(gx, (unsigned)((g.Cout + 63) / 64));
+    if (zscore)
+      hipLaunchKernelGGL((conv_kernel<1, 4, 2, 1, true>), grid, dim3(256), 0, s, g);
+    else
+      hipLaunchKernelGGL((conv_kernel<1, 4, 2, 1, false>), grid, dim3(256), 0, s, g);
+  } else {             // 128 x 128 tiles: 2 x 2 waves of 2 x 2 MFMA tiles
+    const dim3 grid(gx, (unsigned)((g.Cout + 127) / 128));
+    if (zscore)
+      hipLaunchKernelGGL((conv_kernel<2, 2, 2, 2, true>), grid, dim3(256), 0, s, g);
+    else
+      hipLaunchKernelGGL((conv_kernel<2, 2, 2, 2, false>), grid, dim3(256), 0, s, g);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int dgs_conv2d_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
+                         const float* bias, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t zscore,
+                         float* out, dgs_stream_t stream) {
+  if (in == nullptr || weight == nullptr || bias == nullptr || out == nullptr) return dgs_fail_arg("conv2d_bias_relu: null pointer");
+  if (n_img < 1 || Cin < 1 || Cout < 1 || IH < 1 || IW < 1) return dgs_fail_arg("conv2d_bias_relu: empty input or output");
+  if (KH < 1 || KW < 1 || KH > 15 || KW > 15 || stride < 1 || pad < 0 || pad >= KH || pad >= KW)
+    return dgs_fail_arg("conv2d_bias_relu: kernel sizes are 1..15, stride >= 1, 0 <= pad < kernel size");
+  if (zscore != 0 && (zscore != 1 || Cin != 3)) return dgs_fail_arg("conv2d_bias_relu: zscore is 0 or 1, and 1 needs Cin = 3");
+  if (IH + 2 * (int64_t)pad < KH || IW + 2 * (int64_t)pad < KW) return dgs_fail_arg("conv2d_bias_relu: image smaller than the kernel");
+  const int64_t OH = (IH + 2 * (int64_t)pad - KH) / stride + 1, OW = (IW + 2 * (int64_t)pad - KW) / stride + 1;
+  if ((int64_t)Cin * IH * IW >= (1ll << 31) || (int64_t)Cin * KH * KW >= (1ll << 23) || (int64_t)n_img * OH * OW >= (1ll << 31) ||
+      Cout > 65535 * 64)
+    return dgs_fail_arg("conv2d_bias_relu: sizes beyond the kernel's 32-bit index arithmetic");
+  ConvArgs g;
+  g.in0 = in;
+  g.in1 = in;
+  g.n_half = n_img;
+  g.w = weight;
+  g.bias = bias;
+  g.out = out;
+  g.Cin = Cin, g.IH = IH, g.IW = IW, g.Cout = Cout, g.OH = (int)OH, g.OW = (int)OW;
+  g.KH = KH, g.KW = KW, g.stride = stride, g.pad = pad, g.K = Cin * KH * KW, g.N = (int)(n_img * OH * OW);
+  const hipError_t e = launch_conv(g, zscore != 0, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "conv2d_bias_relu");
+}
+
+size_t dgs_lpips_alex_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
+  LpipsPlan P;
+  return lpips_plan(W, H, n_pairs, P) ? P.total_bytes : 0;
+}
+
+int dgs_lpips_alex(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsAlexWeights* w,
+                   void* tmp, float* out, dgs_stream_t stream) {
+  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr)
+    return dgs_fail_arg("lpips_alex: null pointer");
+  for (int l = 0; l < 5; l++)
+    if (w->conv_w[l] == nullptr || w->conv_b[l] == nullptr || w->lin[l] == nullptr)
+      return dgs_fail_arg("lpips_alex: null pointer among the fifteen weight pointers");
+  if (n_pairs < 1) return dgs_fail_arg("lpips_alex: n_pairs must be at least 1");
+  if (W < LP_MIN || H < LP_MIN) return dgs_fail_arg("lpips_alex: the smallest image the network accepts is 31 x 31 (W and H >= 31)");
+  LpipsPlan P;
+  if (!lpips_plan(W, H, n_pairs, P)) return dgs_fail_arg("lpips_alex: more than 65535 pairs or more pixels than one call covers");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(tmp);
+  float* buf_a = reinterpret_cast<float*>(base);
+  float* buf_b = reinterpret_cast<float*>(base + P.off_b);
+  double* partials = reinterpret_cast<double*>(base + P.off_partials);
+  const int n_img = 2 * n_pairs;
+
+  const float* cur = nullptr;        // the input of the next convolution (after the first: one array of n_img images)
+  int ih = H, iw = W, n_pool = 0;
+  for (int l = 0; l < 5; l++) {
+    const ConvShape& c = LP_CONVS[l];
+    float* tap = (l == 3) ? buf_b : buf_a;
+    ConvArgs g;
+    g.in0 = (l == 0) ? a : cur;
+    g.in1 = (l == 0) ? b : cur + (size_t)n_pairs * c.Cin * ih * iw;
+    g.n_half = n_pairs;
+    g.w = w->conv_w[l];
+    g.bias = w->conv_b[l];
+    g.out = tap;
+    g.Cin = c.Cin, g.IH = ih, g.IW = iw, g.Cout = c.Cout, g.OH = P.oh[l], g.OW = P.ow[l];
+    g.KH = c.k, g.KW = c.k, g.stride = c.stride, g.pad = c.pad, g.K = c.Cin * c.k * c.k, g.N = n_img * P.oh[l] * P.ow[l];
+    hipError_t e = launch_conv(g, l == 0, s);
+    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_alex (convolution)");
+    const int hw = P.oh[l] * P.ow[l];
+    hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[l], (unsigned)n_pairs), dim3(256), 0, s, tap, (int)n_pairs,
+                       c.Cout, hw, w->lin[l], partials + P.taps.first[l]);
+    e = hipGetLastError();
+    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_alex (layer distance)");
+    cur = tap;
+    ih = P.oh[l], iw = P.ow[l];
+    if (c.pool) {
+      const int ph = P.ph[n_pool], pw = P.pw[n_pool];
+      n_pool++;
+      const size_t planes = (size_t)n_img * c.Cout, total = planes * ph * pw;
+      const size_t want = (total + 255) / 256;
+      hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)(want < (1u << 20) ? want : (1u << 20))), dim3(256), 0, s, tap, buf_b, planes,
+                         ih, iw, ph, pw);
+      e = hipGetLastError();
+      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_alex (max-pool)");
+      cur = buf_b;
+      ih = ph, iw = pw;
+    }
+  }
+  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_alex (finish)");
+}
+
+}  // extern "C"

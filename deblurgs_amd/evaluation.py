@@ -43,7 +43,8 @@ n - 1 - p more zero-gradient steps, each with that global step's bias correction
 One difference from the sequential fit: there a forward that overflows its capacity skips ONE step; here it skips the whole
 epoch of its group's rows (all n steps of those rows, zero-gradient ones included) -- dropped() counts the view-steps.
 
-LPIPS is not computed (its network weights are not part of this package); `evaluate` returns (psnr, ssim).
+LPIPS, the third number, needs network weights that are not part of this package: `evaluate(..., lpips=weights)` with a
+caller's lpips.LPIPSWeights returns (psnr, ssim, lpips) (dgs_lpips_alex on the device); without it, (psnr, ssim).
 `initialize_test_pose` (COLMAP registration of unposed test images) and the dataset readers are out of scope.
 """
 import ctypes
@@ -587,14 +588,28 @@ def _write_view(vis_dir, i, image, gt, writer):
 
 
 @torch.no_grad()
-def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir=None, writer=None):
+def _lpips_values(images, gts, weights):
+    """The LPIPS of every (image, gt) pair as host floats: one call with n_pairs = len(images) (a pair's value does not
+    depend on the others of its call), the reference's `.mean().item()` per view."""
+    from . import lpips as _lpips
+    x = torch.stack(list(images))
+    y = torch.stack([g.to(x) for g in gts])
+    return [float(v) for v in _lpips.lpips_layers(x, y, weights)[:, 0].tolist()]
+
+
+@torch.no_grad()
+def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir=None, writer=None, lpips=None):
     """evaluate() with the cameras rendered views_per_call at a time: one K-fused forward-only call per group
-    (render_path.render_group), then the per-view metrics of evaluate() on slot k, summed in the same order."""
+    (render_path.render_group), then the per-view metrics of evaluate() on slot k, summed in the same order (LPIPS: the G
+    views of a call as n_pairs = G)."""
     from . import render_path
     cams = list(cams)
-    psnr_test, ssim_test = 0.0, 0.0
+    psnr_test, ssim_test, lpips_test = 0.0, 0.0, 0.0
     for b, e in render_path.frame_groups(cams, views_per_call):
         images = render_path.render_group(cams[b:e], cloud, bg)["render"]
+        if lpips is not None:
+            for v in _lpips_values([tone_mapping(images[k]) for k in range(e - b)], gt_images[b:e], lpips):
+                lpips_test += v
         for k in range(e - b):
             image = tone_mapping(images[k]).contiguous()
             gt = gt_images[b + k].to(image)
@@ -606,12 +621,17 @@ def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, 
             else:
                 psnr_test += metrics.psnr(image, gt).mean().item()
                 ssim_test += metrics.ssim(image, gt).mean().item()
+    if lpips is not None:
+        return psnr_test / len(cams), ssim_test / len(cams), lpips_test / len(cams)
     return psnr_test / len(cams), ssim_test / len(cams)
 
 
 @torch.no_grad()
-def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_dir=None, writer=None):
-    """test.py:93-129 without LPIPS: (mean PSNR, mean SSIM) over the cameras.  The render of every camera goes through the
+def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_dir=None, writer=None, lpips=None):
+    """test.py:93-129: (mean PSNR, mean SSIM) over the cameras -- and, with lpips = an lpips.LPIPSWeights (on the images'
+    device), (mean PSNR, mean SSIM, mean LPIPS-alex): test.py:120 on the same tone-mapped, unclamped image, one
+    dgs_lpips_alex call per view (per group of views under views_per_call), its value independent of views_per_call.
+    Without `lpips` the two floats are what they were, bit for bit.  The render of every camera goes through the
     forward_only inference path (gaussian_renderer.render under no_grad), is tone-mapped and NOT clamped, and both metrics
     come from one fused kernel per view (metrics.psnr / metrics.ssim).
     views_per_call: None renders one camera per call; a number renders the cameras that many at a time through the
@@ -628,8 +648,8 @@ def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_
         from . import report
         report.fresh_directory(vis_dir)
     if views_per_call is not None:
-        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir, writer)
-    psnr_test, ssim_test = 0.0, 0.0
+        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir, writer, lpips)
+    psnr_test, ssim_test, lpips_test = 0.0, 0.0, 0.0
     n = len(cams)
     for i, (cam, gt) in enumerate(zip(cams, gt_images)):
         image = tone_mapping(gaussian_renderer.render(cam, cloud, bg)["render"]).contiguous()
@@ -642,4 +662,8 @@ def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_
         else:
             psnr_test += metrics.psnr(image, gt).mean().item()
             ssim_test += metrics.ssim(image, gt).mean().item()
+        if lpips is not None:
+            lpips_test += _lpips_values([image], [gt], lpips)[0]
+    if lpips is not None:
+        return psnr_test / n, ssim_test / n, lpips_test / n
     return psnr_test / n, ssim_test / n

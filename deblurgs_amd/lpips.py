@@ -1,0 +1,216 @@
+"""LPIPS with the AlexNet backbone, the third number of the reference's evaluation (test.py:120:
+`lpips(image, gt_image, net_type='alex')`, lpipsPyTorch/modules/{lpips,networks,utils}.py):
+
+    z-score per channel   (x - (-.030, -.088, -.188)) / (.458, .448, .450), BEFORE the first convolution, so the
+                          convolution's zero padding pads the z-scored image
+    AlexNet `features`    conv 3->64 11x11 /4 pad 2, ReLU, max-pool 3x3 /2; conv 64->192 5x5 pad 2, ReLU, max-pool 3x3 /2;
+                          conv 192->384, 384->256, 256->256 3x3 pad 1, each with a ReLU
+    taps                  the five ReLU outputs (modules 2, 5, 8, 10, 12 counted from 1), each before its pool
+    per tap               every pixel's channel vector / (sqrt(sum c^2) + 1e-10); the squared difference of the two maps;
+                          the 1x1 "lin" convolution [1,C,1,1] without bias; the spatial mean
+    result                the sum of the five layer values -- and, for a batch of N pairs, over the batch too: the
+                          reference returns ONE [1,1,1,1] tensor (lpips.py:33-36); `lpips` keeps that, `lpips_layers`
+                          and the C ABI return per-pair values
+
+Inputs are used as they come (no rescaling to [-1, 1]); the smallest image the network accepts is 31 x 31.
+
+The weights are the CALLER's: no file ships with this package and nothing is fetched.  `LPIPSWeights` takes the two
+state dicts a user already has (torchvision's AlexNet and the published LPIPS v0.1 `alex.pth`).  fp32 device inputs run
+dgs_lpips_alex (csrc/lpips.hip: an implicit-GEMM convolution on the f32 matrix cores, a max-pool and a layer-distance
+kernel; no MIOpen, no host synchronisation); anything else (CPU, fp64) runs the torch expressions below.
+tests/golden/lpips_golden.npz pins both paths against the reference's own module.
+"""
+import ctypes
+import glob
+import os
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+MEAN = (-.030, -.088, -.188)                  # networks.py:41-44
+STD = (.458, .448, .450)
+# (Cout, Cin, kernel, stride, pad, pooled afterwards) of the five convolutions; their index in torchvision's `features`
+CONVS = ((64, 3, 11, 4, 2, True), (192, 64, 5, 1, 2, True), (384, 192, 3, 1, 1, False), (256, 384, 3, 1, 1, False),
+         (256, 256, 3, 1, 1, False))
+FEATURE_INDEX = (0, 3, 6, 8, 10)
+CHANNELS = tuple(c[0] for c in CONVS)
+MIN_SIZE = 31
+
+
+def _pick(sd, names, what):
+    for n in names:
+        if n in sd:
+            return n, sd[n]
+    raise KeyError(f"LPIPS weights: {what} is missing (looked for {' / '.join(repr(n) for n in names)})")
+
+
+def _as_f32(name, t, shape):
+    t = torch.as_tensor(t)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"LPIPS weights: {name!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.detach().to(torch.float32).contiguous()
+
+
+class LPIPSWeights:
+    """The fifteen tensors of LPIPS-alex: `conv_w[i]` [Cout,Cin,k,k], `conv_b[i]` [Cout], `lin[i]` [1,C,1,1]."""
+
+    def __init__(self, conv_w, conv_b, lin):
+        self.conv_w, self.conv_b, self.lin = list(conv_w), list(conv_b), list(lin)
+        self._struct = None
+
+    @classmethod
+    def from_state_dicts(cls, features_sd, lin_sd):
+        """features_sd: torchvision's AlexNet state dict (`features.{0,3,6,8,10}.{weight,bias}`) or the state dict of its
+        `.features` alone (`{0,3,...}.{weight,bias}`).  lin_sd: the published `lin{i}.model.1.weight`, or the reference's
+        renamed `{i}.1.weight` (lpipsPyTorch/modules/utils.py:22-28).  A missing key or a wrong shape raises with the
+        key named."""
+        conv_w, conv_b, lin = [], [], []
+        for i, (idx, (co, ci, k, _, _, _)) in enumerate(zip(FEATURE_INDEX, CONVS)):
+            for part, shape, dst in (("weight", (co, ci, k, k), conv_w), ("bias", (co,), conv_b)):
+                name, t = _pick(features_sd, (f"features.{idx}.{part}", f"{idx}.{part}"), f"features.{idx}.{part}")
+                dst.append(_as_f32(name, t, shape))
+            name, t = _pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight")
+            lin.append(_as_f32(name, t, (1, co, 1, 1)))
+        return cls(conv_w, conv_b, lin)
+
+    @classmethod
+    def load(cls, backbone_path, lin_path):
+        """The two local checkpoint files (torch.load on the CPU, tensors only)."""
+        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu", weights_only=True),
+                                    torch.load(lin_path, map_location="cpu", weights_only=True))
+
+    def tensors(self):
+        return self.conv_w + self.conv_b + self.lin
+
+    @property
+    def device(self):
+        return self.conv_w[0].device
+
+    def to(self, device):
+        mv = lambda ts: [t.to(device) for t in ts]
+        return LPIPSWeights(mv(self.conv_w), mv(self.conv_b), mv(self.lin))
+
+    def struct(self):
+        """The DgsLpipsAlexWeights of these tensors (they stay alive with this object)."""
+        if self._struct is None:
+            s = _lib.DgsLpipsAlexWeights()
+            for i in range(5):
+                s.conv_w[i], s.conv_b[i], s.lin[i] = self.conv_w[i].data_ptr(), self.conv_b[i].data_ptr(), self.lin[i].data_ptr()
+            self._struct = s
+        return self._struct
+
+
+def _batched(x, y):
+    if x.shape != y.shape or x.dim() not in (3, 4) or x.shape[-3] != 3:
+        raise ValueError(f"lpips takes two [3,H,W] or [N,3,H,W] tensors of one shape (got {tuple(x.shape)}, {tuple(y.shape)})")
+    if x.dim() == 3:
+        x, y = x[None], y[None]
+    if x.shape[-1] < MIN_SIZE or x.shape[-2] < MIN_SIZE:
+        raise ValueError(f"lpips needs images of at least {MIN_SIZE} x {MIN_SIZE} pixels (got {x.shape[-2]} x {x.shape[-1]})")
+    return x, y
+
+
+def _features_torch(x, w):
+    """The five normalised taps of x [N,3,H,W] (networks.py:53-66) in x's dtype on x's device."""
+    t = lambda a: a.to(device=x.device, dtype=x.dtype)
+    x = (x - t(torch.tensor(MEAN))[None, :, None, None]) / t(torch.tensor(STD))[None, :, None, None]
+    out = []
+    for i, (_, _, _, stride, pad, pool) in enumerate(CONVS):
+        x = F.relu(F.conv2d(x, t(w.conv_w[i]), t(w.conv_b[i]), stride=stride, padding=pad))
+        out.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10))
+        if pool:
+            x = F.max_pool2d(x, kernel_size=3, stride=2)
+    return out
+
+
+def _layers_torch(x, y, w):
+    fx, fy = _features_torch(x, w), _features_torch(y, w)
+    res = [F.conv2d((a - b) ** 2, w.lin[i].to(device=x.device, dtype=x.dtype)).mean((2, 3)) for i, (a, b) in enumerate(zip(fx, fy))]
+    layers = torch.cat(res, dim=1)                                           # [N,5]
+    return torch.cat([layers.sum(dim=1, keepdim=True), layers], dim=1)       # [N,6]
+
+
+def _fused_ok(x, y):
+    return (x.device.type == "cuda" and y.device == x.device and x.dtype == torch.float32 and y.dtype == torch.float32)
+
+
+def lpips_layers(x, y, weights):
+    """[N,6] = (total, layer 1..5) per pair of x, y ([3,H,W] or [N,3,H,W]).  fp32 device inputs: one dgs_lpips_alex call
+    on the current stream (the weights must live on that device), no host synchronisation; otherwise the torch
+    expressions in the inputs' dtype."""
+    x, y = _batched(x, y)
+    if not _fused_ok(x, y):
+        return _layers_torch(x, y, weights)
+    if weights.device != x.device:
+        raise RuntimeError(f"lpips: the weights are on {weights.device}, the images on {x.device} (use weights.to(device))")
+    x, y = x.contiguous(), y.contiguous()
+    L = _lib.lib()
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    tmp = torch.empty(L.dgs_lpips_alex_tmp_bytes(W, H, N), dtype=torch.uint8, device=x.device)
+    out = torch.empty((N, 6), dtype=torch.float32, device=x.device)
+    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(L.dgs_lpips_alex(x.data_ptr(), y.data_ptr(), N, W, H, ctypes.byref(weights.struct()), tmp.data_ptr(),
+                                out.data_ptr(), st), "dgs_lpips_alex")
+    return out
+
+
+def conv2d_bias_relu(x, weight, bias, stride=1, padding=0, zscore=False):
+    """relu(conv2d(x, weight, bias, stride, padding)) of fp32 device tensors through dgs_conv2d_bias_relu, the convolution
+    kernel of dgs_lpips_alex on its own (x [N,Cin,H,W]; zscore: the first layer's fused z-score, Cin = 3).  No fallback."""
+    if not (_fused_ok(x, weight) and _fused_ok(x, bias)) or x.dim() != 4 or weight.dim() != 4:
+        raise RuntimeError("conv2d_bias_relu needs float32 tensors on one HIP device: x [N,Cin,H,W], weight [Cout,Cin,KH,KW]")
+    x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
+    N, Cin, IH, IW = (int(v) for v in x.shape)
+    Cout, _, KH, KW = (int(v) for v in weight.shape)
+    if weight.shape[1] != Cin or tuple(bias.shape) != (Cout,):
+        raise ValueError("conv2d_bias_relu: weight is [Cout,Cin,KH,KW] and bias [Cout]")
+    OH, OW = (IH + 2 * padding - KH) // stride + 1, (IW + 2 * padding - KW) // stride + 1
+    out = torch.empty((N, Cout, max(OH, 0), max(OW, 0)), dtype=torch.float32, device=x.device)
+    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.lib().dgs_conv2d_bias_relu(x.data_ptr(), N, Cin, IH, IW, weight.data_ptr(), bias.data_ptr(), Cout, KH, KW,
+                                               int(stride), int(padding), int(bool(zscore)), out.data_ptr(), st),
+               "dgs_conv2d_bias_relu")
+    return out
+
+
+def lpips(x, y, weights):
+    """The reference's criterion (lpips.py:28-36): [3,H,W] or [N,3,H,W] in, ONE [1,1,1,1] tensor out -- the sum over the
+    five layers and over the batch."""
+    return lpips_layers(x, y, weights)[:, 0].sum().reshape(1, 1, 1, 1)
+
+
+# ---- the weights the drop-in `lpipsPyTorch.lpips` uses
+_default = {}
+
+
+def set_default_weights(weights):
+    """The weights `deblurgs_amd/dropin/lpipsPyTorch` evaluates with (None: forget them)."""
+    _default.clear()
+    if weights is not None:
+        _default[weights.device] = weights
+
+
+def default_weights(device):
+    """The default weights on `device`: those of set_default_weights, else the two files a user of torchvision and of the
+    LPIPS package already has in torch.hub's checkpoint directory.  Only local files are opened; nothing is fetched."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device in _default:
+        return _default[device]
+    if _default:
+        w = next(iter(_default.values())).to(device)
+    else:
+        ckpt = os.path.join(torch.hub.get_dir(), "checkpoints")
+        backbone = sorted(glob.glob(os.path.join(ckpt, "alexnet-owt-*.pth")))
+        lin = os.path.join(ckpt, "alex.pth")
+        if not backbone or not os.path.exists(lin):
+            raise FileNotFoundError(
+                f"LPIPS needs two weight files and neither ships with this package: torchvision's AlexNet checkpoint "
+                f"(alexnet-owt-*.pth) and the LPIPS v0.1 linear layers (alex.pth).  Put both into {ckpt}, or call "
+                "deblurgs_amd.lpips.set_default_weights(LPIPSWeights.load(backbone_path, lin_path)).")
+        w = LPIPSWeights.load(backbone[-1], lin).to(device)
+    _default[device] = w
+    return w

@@ -7,7 +7,8 @@ Everything else the reference's signatures accept -- CPU tensors, batches, other
 size_average=False -- runs the torch expressions below on whatever device the tensors live on.
 tests/golden/metrics_golden.npz pins both paths against the reference's own functions.
 
-LPIPS, the third number the reference reports, is not implemented: its network weights are not part of this package.
+LPIPS, the third number the reference reports, is `lpips(x, y, weights)` (deblurgs_amd/lpips.py, re-exported here): the
+operator is part of this package (dgs_lpips_alex), its network weights are the caller's.
 """
 import ctypes
 from math import exp
@@ -16,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .lpips import lpips, lpips_layers  # noqa: F401  (the third metric of test.py:118-120)
 
 
 def _gaussian(window_size, sigma):

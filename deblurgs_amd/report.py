@@ -21,7 +21,7 @@ installed) and pinned by tests/golden/report_golden.npz.  PNG files are written 
 .npy; every writer argument is a callable writer(path, array) that takes the place of the file.
 
 Out of scope: colorize with a mask or a colour bar (cv2, a matplotlib canvas), camera-cone drawings, alignment plots,
-videos, LPIPS.
+videos.  (LPIPS, the third number of evaluate(), is deblurgs_amd/lpips.py: evaluate(..., lpips=weights).)
 """
 import ctypes
 import os

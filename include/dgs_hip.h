@@ -656,6 +656,44 @@ int dgs_report_images(const float* x, int32_t K, int32_t mean, int32_t H, int32_
 int dgs_scalar_colorize(const float* x, uint64_t n, const double* lo_hi, const uint8_t* lut, uint8_t* out,
                         dgs_stream_t stream);
 
+/* ---- LPIPS (additions to ABI 15; test.py:120, lpipsPyTorch/modules/{lpips,networks,utils}.py of the reference) ----
+ * The reference's third evaluation number, lpips(image, gt_image, net_type='alex'), with CALLER-SUPPLIED weights: the
+ * library ships none and fetches none.  The AlexNet `features` shapes and the z-score constants are fixed in the library:
+ *   conv_w[0..4]  [64,3,11,11] [192,64,5,5] [384,192,3,3] [256,384,3,3] [256,256,3,3]   (torchvision features.0/3/6/8/10)
+ *   conv_b[0..4]  [64] [192] [384] [256] [256]
+ *   lin[0..4]     [1,C,1,1], C = 64, 192, 384, 256, 256                                  (LPIPS v0.1 lin{i}.model.1.weight)
+ * all fp32, contiguous, in device memory. */
+typedef struct DgsLpipsAlexWeights {
+  const float* conv_w[5];
+  const float* conv_b[5];
+  const float* lin[5];
+} DgsLpipsAlexWeights;
+/* a, b [n_pairs,3,H,W] fp32, used as they come (no rescaling); out [n_pairs,6] = per pair (total, layer 1..5):
+ * z-score (x - (-.030, -.088, -.188)) / (.458, .448, .450) before the first convolution (whose zero padding so pads the
+ * z-scored image); conv 11x11 /4 pad 2, ReLU, max-pool 3x3 /2, conv 5x5 pad 2, ReLU, max-pool 3x3 /2, three conv 3x3 pad 1
+ * each with a ReLU; per ReLU output (before its pool): every pixel's channel vector / (sqrt(sum c^2) + 1e-10), the squared
+ * difference of the two maps under the lin weights, the spatial mean; total = the sum of the five.  (The reference's
+ * function sums a batch into one number; this returns the pairs one by one.)  fp32 throughout; the convolutions run on the
+ * f32-input matrix cores (dgs_conv2d_bias_relu).  Stream-explicit, caller-owned memory, no host synchronisation, no
+ * float atomics: a pair's six numbers do not depend on the other pairs of the call or on n_pairs, two runs are bitwise
+ * equal, lpips(x, x) is exactly 0 in all six and lpips(x, y) == lpips(y, x) bitwise.
+ * tmp >= dgs_lpips_alex_tmp_bytes(W, H, n_pairs) bytes (0: arguments the call refuses), 256-byte aligned.  Refused before
+ * any HIP call: a NULL pointer (the fifteen of `w` included), n_pairs < 1 (or above 65535), W or H below 31 -- the
+ * smallest image the network accepts, as the reference raises at 30. */
+size_t dgs_lpips_alex_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs);
+int dgs_lpips_alex(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsAlexWeights* w,
+                   void* tmp, float* out, dgs_stream_t stream);
+/* The convolution of the above on its own: out [n_img,Cout,OH,OW] = relu(conv2d(in [n_img,Cin,IH,IW], weight
+ * [Cout,Cin,KH,KW], bias [Cout], stride, zero padding pad)), OH = (IH + 2 pad - KH) / stride + 1.  An implicit GEMM
+ * C[Cout x N] = W[Cout x K] . patches[K x N], K = Cin KH KW in the weight's own order, N over the output pixels of all
+ * images, patches gathered on the fly, on v_mfma_f32_32x32x2_f32.  Every output element is: per 32 consecutive k one
+ * k-ordered fmaf chain from 0, the chains' results added in order with a compensated (Kahan) fp32 sum, + bias, ReLU
+ * (a NaN passes) -- whatever its place in the call.  zscore = 1 (Cin = 3): the input is z-scored as above on the way in,
+ * the padding stays 0.  KH, KW in 1..15, pad below both.  `out` must not overlap `in`. */
+int dgs_conv2d_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
+                         const float* bias, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t zscore,
+                         float* out, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
