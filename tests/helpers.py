@@ -72,20 +72,109 @@ def unstable_pixels(st, alpha_tol=5e-7, power_tol=1e-4, T_tol=1e-8):
     return flag.reshape(H, W)
 
 
-def exempt_pixels(scene, K, states, **kw):
+def oracle_pixel_walk(st, y, x):
+    """The oracle's traversal of pixel (x, y), restated in fp32 numpy (dgs_oracle_render): one record
+    (pos, Gaussian, power, alpha, T before the pair, contributes) per list entry the pixel evaluates; pos is 1-based."""
+    gx = (st["W"] + 15) // 16
+    r0, r1 = (int(v) for v in st["ranges"][(y // 16) * gx + x // 16])
+    out, T = [], np.float32(1.0)
+    for pos, g in enumerate(st["point_list"][r0:r1], start=1):
+        c = st["conic_opacity"][g]
+        dx, dy = st["means2D"][g, 0] - np.float32(x), st["means2D"][g, 1] - np.float32(y)
+        power = np.float32(-0.5) * (c[0] * dx * dx + c[2] * dy * dy) - c[1] * dx * dy
+        alpha = np.float32(min(np.float32(0.99), c[3] * np.exp(power)))
+        ok = bool(power <= 0 and alpha >= np.float32(1.0 / 255.0))
+        test_T = T * (np.float32(1.0) - alpha)
+        if ok and test_T < np.float32(1e-4):
+            out.append((pos, int(g), float(power), float(alpha), float(T), False))
+            break
+        out.append((pos, int(g), float(power), float(alpha), float(T), ok))
+        if ok:
+            T = test_T
+    return out
+
+
+_CHK_MUL_INV = pow(2654435761, -1, 1 << 32)
+
+
+def describe_exempt(st, mask, hip_checksum, hip_n_contrib, limit=8):
+    """For (at most `limit` of) the pixels of `mask`: the pixel, the two last contributors, and the ORACLE's numbers of the
+    deciding pair -- the list position that a single flipped decision leaves in the checksum difference (pos * 2654435761
+    mod 2^32) when there is one, else the evaluated pair that sits closest to the alpha threshold."""
+    margin = oracle.unstable(st)
+    lines = []
+    hc, hn = np.asarray(hip_checksum).reshape(-1).view(np.uint32), np.asarray(hip_n_contrib).reshape(-1).view(np.uint32)
+    for y, x in np.argwhere(mask)[:limit]:
+        y, x = int(y), int(x)
+        pix = y * st["W"] + x
+        walk = oracle_pixel_walk(st, y, x)
+        diff = (int(hc[pix]) - int(st["contrib_checksum"][pix])) % (1 << 32)
+        extra, dropped = (diff * _CHK_MUL_INV) % (1 << 32), ((-diff) * _CHK_MUL_INV) % (1 << 32)
+        by_pos = {w[0]: w for w in walk}
+        if diff and extra in by_pos:
+            why, w = "the HIP forward alone blends", by_pos[extra]
+        elif diff and dropped in by_pos:
+            why, w = "the HIP forward alone skips", by_pos[dropped]
+        elif walk:
+            why = "several decisions differ; closest to the alpha threshold:"
+            w = min(walk, key=lambda r: abs(r[3] - 1.0 / 255.0))
+        else:
+            why, w = "empty list", (0, -1, 0.0, 0.0, 1.0, False)
+        lines.append(f"pixel (x={x}, y={y}){'' if margin[y, x] else ' OUTSIDE the margin mask'}: last contributor HIP "
+                     f"{int(hn[pix])} / oracle {int(st['n_contrib'][pix])}; {why} list position {w[0]} (Gaussian {w[1]}): "
+                     f"alpha {w[3]:.9g} (1/255 = {1 / 255:.9g}), power {w[2]:.6g}, T {w[4]:.6g}")
+    return "\n   ".join(lines)
+
+
+def exempt_cap(st):
+    """The most pixels of one subframe that may be exempt when the caller names no figure of its own."""
+    return max(2e-4 * st["H"] * st["W"], 4)
+
+
+def capped_exempt_masks(states, hip_checksum, hip_n_contrib, cap=None, what="exempt pixels"):
+    """[len(states)] masks [H,W] of the pixels where the HIP forward (hip_*: [K', H*W] of a tile_cull = 0 forward) and the
+    oracle's took a different per-pair decision -- and the ceiling on them, asserted HERE so that every caller inherits
+    it.  A kernel regression in a per-pair decision (a cull that drops a contributing pair, a wrong quadrant mask, a
+    termination off by one entry) IS such a difference: without a ceiling it would exempt itself.  Per subframe
+
+        exempt <= max(2e-4 H W, 4)    (or the caller's `cap`: the scene's margin count, from the oracle alone)
+        exempt <= margin + 2          (margin = oracle.unstable(state): the pixels where the ORACLE's own traversal sits
+                                       within a rounding error of a threshold; computed only where exempt > 2)
+
+    DGS_EXEMPT_LOG=<file>: one line per call with the exempt and margin counts (the margins are then always computed)."""
+    masks, counts, margins = [], [], []
+    log = os.environ.get("DGS_EXEMPT_LOG")
+    for i, st in enumerate(states):
+        hc = np.asarray(hip_checksum[i]).reshape(-1).view(np.uint32)
+        hn = np.asarray(hip_n_contrib[i]).reshape(-1).view(np.uint32)
+        d = ((hc != st["contrib_checksum"]) | (hn != st["n_contrib"])).reshape(st["H"], st["W"])
+        n = int(d.sum())
+        masks.append(d)
+        counts.append(n)
+        limit = exempt_cap(st) if cap is None else cap
+        margin = int(oracle.unstable(st).sum()) if (n > 2 or log) else None
+        margins.append(margin)
+        if n > limit or (margin is not None and n > margin + 2):
+            raise AssertionError(
+                f"{what}, subframe {i}: {n} pixels of {st['H'] * st['W']} differ from the oracle in a per-pair decision "
+                f"(allowed {limit:g}, and the oracle's margin mask + 2 = {margin if margin is not None else '?'} + 2):\n   "
+                + describe_exempt(st, d, hc, hn))
+    if log:
+        with open(log, "a") as f:
+            f.write(f"{os.environ.get('PYTEST_CURRENT_TEST', what)} | {states[0]['W']}x{states[0]['H']} | exempt {counts} "
+                    f"| margin {margins}\n")
+    return masks
+
+
+def exempt_pixels(scene, K, states, cap=None, **kw):
     """[K] masks [H,W]: the pixels where the HIP forward and the oracle's took a DIFFERENT per-pair decision -- their
     contributor checksums (DgsForwardOut.debug_contrib_checksum: a tile_cull = 0 forward through the C ABI; dgs_oracle_render)
     or their last contributors differ.  What the parity tests exempt from the 1e-4 bars since round 6 (the margin rule of
-    unstable_pixels / oracle.unstable exempted every pixel NEAR a threshold: hundreds of times more).  kw: what
-    hip_forward_state takes (sh_degree, use_sigmoid, colors_precomp, cov3D_precomp, scale_modifier)."""
+    unstable_pixels / oracle.unstable exempted every pixel NEAR a threshold: hundreds of times more).  Their number is
+    bounded here (capped_exempt_masks).  kw: what hip_forward_state takes (sh_degree, use_sigmoid, colors_precomp,
+    cov3D_precomp, scale_modifier)."""
     st = hip_forward_state(scene, K, checksum=True, **kw)
-    masks = []
-    for k in range(K):
-        o = states[k]
-        d = (st["contrib_checksum"][k].reshape(-1) != o["contrib_checksum"]) | \
-            (st["n_contrib"][k].reshape(-1) != o["n_contrib"])
-        masks.append(d.reshape(o["H"], o["W"]))
-    return masks
+    return capped_exempt_masks(states[:K], st["contrib_checksum"], st["n_contrib"], cap=cap)
 
 
 # --------------------------------------------------------------------------------------------- HIP side
@@ -348,10 +437,11 @@ class OracleRun:
     algorithm differ from each other; they are large exactly where a gradient component is ill-conditioned (scale /
     rotation behind the covariance chain, the view matrix)."""
 
-    def __init__(self, scene, K, margin_masks=True, exact=False, **kw):
+    def __init__(self, scene, K, margin_masks=True, exact=False, cap=None, **kw):
         """margin_masks=False: the caller will install the exact disagreement masks (use_exact_masks) and the oracle's
         threshold-margin masks are not computed.  exact=True: the masks are exempt_pixels() of this scene (a HIP forward
-        with contributor checksums is run here: needs the GPU)."""
+        with contributor checksums is run here: needs the GPU); their number is bounded there (cap: see
+        capped_exempt_masks)."""
         self.scene, self.K, self.kw = scene, K, kw
         margin_masks = margin_masks and not exact
         oracle.use_openmp(True)
@@ -364,23 +454,24 @@ class OracleRun:
             st.pop("keys_unsorted", None)
             st.pop("vals_unsorted", None)
         if exact:
-            self.unstable = exempt_pixels(scene, K, self.states, **kw)
+            self.unstable = exempt_pixels(scene, K, self.states, cap=cap, **kw)
 
-    def use_exact_masks(self, hip_checksum, hip_n_contrib, ks=None):
+    def use_exact_masks(self, hip_checksum, hip_n_contrib, ks=None, cap=None):
         """Replaces the margin masks (every pixel whose ORACLE traversal sits within a margin of a threshold: 0.5 % of the
         pixels at the metric size) by the pixels where the HIP traversal and the oracle's really took a different per-pair
         decision: their contributor checksums (DgsForwardOut.debug_contrib_checksum / dgs_oracle_render) or their last
         contributors differ.  hip_* are [K', H*W] arrays of a tile_cull = 0 forward (positions in the reference's lists),
-        for the subframes ks of this run (default: all).  Returns the exempt pixel count per subframe."""
+        for the subframes ks of this run (default: all).  Returns the exempt pixel count per subframe; it is bounded
+        here (capped_exempt_masks), per subframe."""
         ks = list(range(self.K)) if ks is None else list(ks)
-        counts = []
-        for i, k in enumerate(ks):
-            st = self.states[k]
-            d = (np.asarray(hip_checksum[i]).view(np.uint32).reshape(-1) != st["contrib_checksum"]) | \
-                (np.asarray(hip_n_contrib[i]).view(np.uint32).reshape(-1) != st["n_contrib"])
-            self.unstable[k] = d.reshape(st["H"], st["W"])
-            counts.append(int(d.sum()))
-        return counts
+        oracle.use_openmp(True)
+        try:
+            masks = capped_exempt_masks([self.states[k] for k in ks], hip_checksum, hip_n_contrib, cap=cap)
+        finally:
+            oracle.use_openmp(False)
+        for k, d in zip(ks, masks):
+            self.unstable[k] = d
+        return [int(d.sum()) for d in masks]
 
     def subset(self, idx):
         r = OracleRun.__new__(OracleRun)
