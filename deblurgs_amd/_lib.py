@@ -94,6 +94,10 @@ class DgsLpipsAlexWeights(ctypes.Structure):
     _fields_ = [("conv_w", ctypes.c_void_p * 5), ("conv_b", ctypes.c_void_p * 5), ("lin", ctypes.c_void_p * 5)]
 
 
+class DgsLpipsVggWeights(ctypes.Structure):
+    _fields_ = [("conv_w", ctypes.c_void_p * 13), ("conv_b", ctypes.c_void_p * 13), ("lin", ctypes.c_void_p * 5)]
+
+
 ADAM_MAX_GROUPS = 16
 ABI_VERSION = 15           # DGS_ABI_VERSION of include/dgs_hip.h (tests/test_abi.py keeps the two in step)
 
@@ -224,6 +228,12 @@ EXPORTS = {
                        [ctypes.c_void_p] * 3),
     "dgs_conv2d_bias_relu": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2 +
                              [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 2),
+    "dgs_lpips_vgg_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
+    "dgs_lpips_vgg": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 3 + [ctypes.POINTER(DgsLpipsVggWeights)] +
+                      [ctypes.c_void_p] * 3),
+    "dgs_conv3x3_bias_relu": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2 +
+                              [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2),
+    "dgs_maxpool2x2": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 2),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

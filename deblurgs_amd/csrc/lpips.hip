@@ -1,9 +1,12 @@
 // lpips.hip -- LPIPS with the AlexNet backbone, the third number of the reference's evaluation (test.py:120,
-// lpipsPyTorch/modules/{lpips,networks,utils}.py), with caller-supplied weights:
+// lpipsPyTorch/modules/{lpips,networks,utils}.py), and with the VGG16 backbone, the one metrics.py:74 reports, with
+// caller-supplied weights:
 //   * conv_kernel: ONE implicit-GEMM fp32 convolution for all five layers on the f32-input matrix cores
 //     (v_mfma_f32_32x32x2_f32), with bias + ReLU in the epilogue and the z-score of the input fused into the first
 //     layer's gather;
 //   * maxpool_kernel: 3 x 3 stride 2, floor, no padding;
+//   * conv3x3_kernel: VGG's 3 x 3 / stride 1 / pad 1 convolutions from an input halo tile in LDS, on the same matrix
+//     cores with the same epilogue; maxpool2x2_kernel: VGG's 2 x 2 stride 2 pool;
 //   * layer_distance_kernel + lpips_finish_kernel: per tap the channel-normalised squared difference under the "lin"
 //     weights, reduced over space in block order.
 // Built with -ffp-contract=off (deblurgs_amd/build.py): the compensated sum of the convolution below is only what it says
@@ -225,6 +228,209 @@ maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, size_t pla
   }
 }
 
+// ---- VGG16: every convolution is 3 x 3, stride 1, pad 1, so the patches need not be gathered element by element
+constexpr int V_ROWS = 4, V_COLS = 32;           // output pixels of a block: one rectangle of one image
+constexpr int V_PITCH = V_COLS + 2;              // halo row pitch, floats
+constexpr int V_CH = (V_ROWS + 2) * V_PITCH;     // halo of one channel: 204 floats
+constexpr int V_MIN = 16;                        // smallest image: four floor pools leave 1 x 1
+
+// relu(conv2d(x, w, b, stride 1, pad 1)), 3 x 3: a block owns BM = WM TM 32 output channels by 4 rows x 32 columns of ONE
+// image (tiles never straddle images or wrap rows); wave (wm, wn) a TM x TN grid of 32 x 32 MFMA tiles, an MFMA tile 32
+// channels by the 32 columns of one row.  Per chunk of CC input channels the 6 x 34 halo of each channel goes to LDS
+// once (s_h[ci][row][col], zeros outside the image and past Cin; first layer: z-scored inside the image only) together
+// with the matching slab of the [Cout,Cin,3,3] weights, transposed (s_w[(ky, kx)][ci][m], pitch BM + 1).  Every staged
+// halo value is used nine times: for (ky, kx) the B operand of lane l is s_h[ci = 2 j + (l >> 5)][row + ky][kx + (l & 31)]
+// -- one ds_read_b32 whose two lane groups each read 32 consecutive floats, conflict-free whatever the pitch (a group is
+// served on its own, bank = dword address mod 32).  The pitch is 34 = no padding at all: a channel's halo, and the
+// chunk's, is one dense run of floats which the threads write in index order, 32 consecutive dwords per lane group, so
+// the ds_write_b32 are conflict-free too.  The A operand is s_w[(ky, kx)][ci][32 consecutive m].  No im2col copy, no k
+// table, no bounds test between the barrier and the last MFMA of a chunk.
+// Pipeline: LDS is double-buffered and there is ONE barrier per chunk -- the global loads of chunk c + 1 are issued into
+// registers before the MFMAs of chunk c and stored after them into the other buffer, which every wave left before the
+// barrier of chunk c.
+// CC: 8 for the 128-channel tile (it runs at one wave per SIMD whatever the chunk -- three accumulator sets of 64
+// registers -- and the longer chunk halves the compensated sums, the zeroing and the barriers per MFMA: 87 360 B of LDS),
+// 4 for the 64-channel tile (25 248 B; with 8 it would lose its second wave per SIMD to the staging registers).
+// Numerics: per chunk one chain of L = 9 CC terms (72 / 36) from 0 in the k order (ky, kx, ci) -- for each of the nine
+// weights in row-major order the chunk's channels in order (terms past Cin are 0 x 0); the chunks' sums are added in
+// channel order with conv_kernel's compensated sum; then bias, then ReLU (a NaN passes).  An element's arithmetic depends
+// on the layer shape and the image size only, never on n_img or on the image's place in the call.
+template <int WM, int WN, int TM, int TN, int CC, bool ZSCORE>
+__global__ void __launch_bounds__(256) conv3x3_kernel(const ConvArgs g, const int tiles_x, const int tiles_per_img) {
+  constexpr int BM = WM * TM * 32, BMP = BM + 1;
+  constexpr int V_L = 9 * CC, V_HALO = CC * V_CH, V_NH = (V_HALO + 255) / 256;
+  constexpr int NW = BM * V_L / 256;             // weights a thread stages per chunk
+  static_assert(WM * WN == 4 && WN * TN == V_ROWS && (BM * V_L) % 256 == 0, "four waves, four rows");
+  __shared__ float s_w[2][V_L * BMP];
+  __shared__ float s_h[2][V_HALO];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int img = blockIdx.x / tiles_per_img, tile = blockIdx.x - img * tiles_per_img;
+  const int ty = tile / tiles_x;
+  const int y0 = ty * V_ROWS, x0 = (tile - ty * tiles_x) * V_COLS;
+  const int m0 = blockIdx.y * BM;
+  const int ihw = g.IH * g.IW;
+  const float* src = (img < g.n_half) ? g.in0 + (size_t)img * g.Cin * ihw : g.in1 + (size_t)(img - g.n_half) * g.Cin * ihw;
+
+  // this thread's halo elements: where they lie in the image does not change from chunk to chunk
+  int h_off[V_NH], h_ci[V_NH];   // h_ci < 0: outside the image (or past the halo's end): stays 0
+#pragma unroll
+  for (int i = 0; i < V_NH; i++) {
+    const int e = t + 256 * i;
+    const int ci = e / V_CH, rem = e - ci * V_CH;
+    const int r = rem / V_PITCH, c = rem - r * V_PITCH;
+    const int iy = y0 - 1 + r, ix = x0 - 1 + c;
+    const bool in = e < V_HALO && (unsigned)iy < (unsigned)g.IH && (unsigned)ix < (unsigned)g.IW;
+    h_ci[i] = in ? ci : -1;
+    h_off[i] = in ? ci * ihw + iy * g.IW + ix : 0;
+  }
+
+  f32x16 tot[TM][TN], comp[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; i++)
+#pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        tot[i][j][r] = 0.0f;
+        comp[i][j][r] = 0.0f;
+      }
+
+  float rw[NW], rh[V_NH];
+  auto load_chunk = [&](int c0) {   // c0: the chunk's first input channel
+#pragma unroll
+    for (int i = 0; i < NW; i++) {  // 36 consecutive floats of the weight tensor per output channel
+      const int e = t + 256 * i;
+      const int ml = e / V_L, r = e - ml * V_L;
+      const int m = m0 + ml;
+      rw[i] = (m < g.Cout && c0 + r / 9 < g.Cin) ? g.w[(size_t)m * g.K + c0 * 9 + r] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < V_NH; i++) {
+      const int ci = h_ci[i];
+      float v = (ci >= 0 && c0 + ci < g.Cin) ? src[(size_t)c0 * ihw + h_off[i]] : 0.0f;
+      if (ZSCORE) {  // networks.py:41-51, conv_kernel's expression; outside the image the halo stays 0
+        const float mean = ci == 0 ? -.030f : (ci == 1 ? -.088f : -.188f);
+        const float sd = ci == 0 ? .458f : (ci == 1 ? .448f : .450f);
+        v = (ci >= 0 && ci < g.Cin) ? (v - mean) / sd : 0.0f;
+      }
+      rh[i] = v;
+    }
+  };
+  auto store_chunk = [&](int b) {
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+      const int e = t + 256 * i;
+      const int ml = e / V_L, r = e - ml * V_L;
+      const int ci = r / 9, tap = r - ci * 9;
+      s_w[b][(tap * CC + ci) * BMP + ml] = rw[i];
+    }
+#pragma unroll
+    for (int i = 0; i < V_NH; i++)
+      if (t + 256 * i < V_HALO) s_h[b][t + 256 * i] = rh[i];
+  };
+
+  const int n_chunks = (g.Cin + CC - 1) / CC;
+  load_chunk(0);
+  for (int c = 0; c < n_chunks; c++) {
+    const int b = c & 1;
+    store_chunk(b);
+    __syncthreads();
+    if (c + 1 < n_chunks) load_chunk((c + 1) * CC);
+
+    const float* wb = s_w[b] + (lane >> 5) * BMP + wm * TM * 32 + (lane & 31);
+    const float* hb = s_h[b] + (lane >> 5) * V_CH + wn * TN * V_PITCH + (lane & 31);
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int j = 0; j < TN; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+    // k-step s = (weight s / (CC / 2), channel pair s % (CC / 2)); the operands of step s + 1 are read from LDS before
+    // the MFMAs of step s, so that at one wave per SIMD the ds_read latency hides behind them
+    constexpr int STEPS = 9 * CC / 2;
+    float a[2][TM], bv[2][TN];
+    auto read_step = [&](int s, int p) {
+      const int tap = s / (CC / 2), cc = 2 * (s - tap * (CC / 2));
+      const int ky = tap / 3, kx = tap - 3 * ky;
+#pragma unroll
+      for (int i = 0; i < TM; i++) a[p][i] = wb[(tap * CC + cc) * BMP + i * 32];
+#pragma unroll
+      for (int j = 0; j < TN; j++) bv[p][j] = hb[cc * V_CH + (j + ky) * V_PITCH + kx];
+    };
+    read_step(0, 0);
+#pragma unroll
+    for (int s = 0; s < STEPS; s++) {
+      if (s + 1 < STEPS) read_step(s + 1, (s + 1) & 1);
+#pragma unroll
+      for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < TN; j++)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s & 1][i], bv[s & 1][j], acc[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int j = 0; j < TN; j++) {  // Kahan, as conv_kernel
+        const f32x16 y = acc[i][j] - comp[i][j];
+        const f32x16 s = tot[i][j] + y;
+        comp[i][j] = (s - tot[i][j]) - y;
+        tot[i][j] = s;
+      }
+  }
+
+  // bias + ReLU; C/D layout as in conv_kernel: per register a lane group writes 32 consecutive pixels of one channel
+  const int ohw = g.OH * g.OW;
+#pragma unroll
+  for (int j = 0; j < TN; j++) {
+    const int y = y0 + wn * TN + j, x = x0 + (lane & 31);
+    if (y >= g.OH || x >= g.OW) continue;
+    float* dst = g.out + (size_t)img * g.Cout * ohw + y * g.OW + x;
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (m < g.Cout) {
+          const float v = tot[i][j][r] + g.bias[m];
+          dst[(size_t)m * ohw] = (v < 0.0f) ? 0.0f : v;
+        }
+      }
+  }
+}
+
+// max_pool2d(kernel 2, stride 2): floor, no padding; a NaN in the window is the result (the window in row-major order,
+// torch's update rule).  A thread makes two neighbouring outputs; vec (IW a multiple of 4, `in` 16-byte and `out`
+// 8-byte aligned): from two 16-byte loads, one 8-byte store.
+__device__ __forceinline__ float lp_max4(float a, float b, float c, float d) {
+  float m = a;
+  m = (b > m || b != b) ? b : m;
+  m = (c > m || c != c) ? c : m;
+  m = (d > m || d != d) ? d : m;
+  return m;
+}
+
+__global__ void __launch_bounds__(256)
+maxpool2x2_kernel(const float* __restrict__ in, float* __restrict__ out, size_t planes, int IH, int IW, int PH, int PW, int vec) {
+  const int PW2 = (PW + 1) / 2;
+  const size_t per_plane = (size_t)PH * PW2, total = planes * per_plane;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t plane = e / per_plane;
+    const int p = (int)(e - plane * per_plane);
+    const int y = p / PW2, x = 2 * (p - y * PW2);
+    const float* s = in + plane * (size_t)IH * IW + (size_t)(2 * y) * IW + 2 * x;
+    float* d = out + plane * (size_t)PH * PW + (size_t)y * PW + x;
+    if (vec) {
+      const float4 r0 = *reinterpret_cast<const float4*>(s), r1 = *reinterpret_cast<const float4*>(s + IW);
+      *reinterpret_cast<float2*>(d) = make_float2(lp_max4(r0.x, r0.y, r1.x, r1.y), lp_max4(r0.z, r0.w, r1.z, r1.w));
+    } else {
+      d[0] = lp_max4(s[0], s[1], s[IW], s[IW + 1]);
+      if (x + 1 < PW) d[1] = lp_max4(s[2], s[3], s[IW + 2], s[IW + 3]);
+    }
+  }
+}
+
 // sum over the 256 threads of a block in a fixed order (as metrics.hip's); valid in thread 0
 __device__ __forceinline__ double lp_block_sum_256(double v, double* red) {
   red[threadIdx.x] = v;
@@ -363,6 +569,84 @@ hipError_t launch_conv(const ConvArgs& g, bool zscore, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- VGG16 (networks.py:88-96): thirteen 3 x 3 convolutions; taps after convolutions 2, 4, 7, 10 (each before its 2 x 2
+// pool) and 13
+constexpr int VGG_N = 13;
+const int VGG_COUT[VGG_N] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+const int VGG_TAP[VGG_N] = {-1, 0, -1, 1, -1, -1, 2, -1, -1, 3, -1, -1, 4};
+
+// Which convolution kernel a VGG layer runs on: a function of the layer shape only (DESIGN.md 7 has the per-layer timings
+// behind it).  The halo-tile kernel won every layer but the first by 8 % and more in every round; on 3 -> 64 channels
+// (14 GFLOP, 1 GB written: bound by the store) it was not on one side of the generic kernel in every round, and a layer
+// it has not won stays on the generic kernel.
+bool vgg_layer_on_conv3x3(int Cin, int Cout) {
+  (void)Cout;
+  return Cin > 3;
+}
+
+hipError_t launch_conv3x3(const ConvArgs& g, int n_img, bool zscore, hipStream_t s) {
+  const int tiles_x = (g.OW + V_COLS - 1) / V_COLS, tiles_per_img = tiles_x * ((g.OH + V_ROWS - 1) / V_ROWS);
+  const unsigned gx = (unsigned)((size_t)n_img * tiles_per_img);
+  if (g.Cout <= 64) {  // 64 channels: wave w takes row w
+    const dim3 grid(gx, (unsigned)((g.Cout + 63) / 64));
+    if (zscore)
+      hipLaunchKernelGGL((conv3x3_kernel<1, 4, 2, 1, 4, true>), grid, dim3(256), 0, s, g, tiles_x, tiles_per_img);
+    else
+      hipLaunchKernelGGL((conv3x3_kernel<1, 4, 2, 1, 4, false>), grid, dim3(256), 0, s, g, tiles_x, tiles_per_img);
+  } else {             // 128 channels: 2 x 2 waves of 2 x 2 MFMA tiles (64 channels by two rows)
+    const dim3 grid(gx, (unsigned)((g.Cout + 127) / 128));
+    if (zscore)
+      hipLaunchKernelGGL((conv3x3_kernel<2, 2, 2, 2, 8, true>), grid, dim3(256), 0, s, g, tiles_x, tiles_per_img);
+    else
+      hipLaunchKernelGGL((conv3x3_kernel<2, 2, 2, 2, 8, false>), grid, dim3(256), 0, s, g, tiles_x, tiles_per_img);
+  }
+  return hipGetLastError();
+}
+
+size_t conv3x3_tiles(int64_t n_img, int64_t H, int64_t W) {
+  return (size_t)(n_img * ((H + V_ROWS - 1) / V_ROWS) * ((W + V_COLS - 1) / V_COLS));
+}
+
+hipError_t launch_maxpool2x2(const float* in, size_t planes, int IH, int IW, float* out, hipStream_t s) {
+  const int PH = IH / 2, PW = IW / 2;
+  const size_t total = planes * (size_t)PH * ((PW + 1) / 2), want = (total + 255) / 256;
+  const int vec = (IW % 4 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(maxpool2x2_kernel, dim3((unsigned)(want < (1u << 20) ? want : (1u << 20))), dim3(256), 0, s, in, out, planes,
+                     IH, IW, PH, PW, vec);
+  return hipGetLastError();
+}
+
+struct VggPlan {
+  int h[5], w[5];       // the taps' sizes
+  size_t off_b, off_partials, total_bytes;   // two ping-pong buffers of the largest layer output [n_img,64,H,W], the partials
+  LpipsTaps taps;
+};
+
+// false: an image below 16 x 16, no pairs, or sizes the kernels' 32-bit arithmetic does not cover
+bool vgg_plan(int W, int H, int n_pairs, VggPlan& P) {
+  if (W < V_MIN || H < V_MIN || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
+  const size_t n_img = 2 * (size_t)n_pairs;
+  // (elements of one image's largest feature map, pixels of a call)
+  if ((size_t)64 * H * W >= ((size_t)1 << 31) || n_img * (size_t)H * W >= ((size_t)1 << 31)) return false;
+  int h = H, w = W;
+  size_t partial = 0;
+  for (int t = 0; t < 5; t++) {
+    P.h[t] = h;
+    P.w[t] = w;
+    P.taps.first[t] = partial;
+    P.taps.blocks[t] = (h * w + 255) / 256;
+    P.taps.hw[t] = (double)h * (double)w;
+    partial += (size_t)n_pairs * P.taps.blocks[t];
+    h /= 2;
+    w /= 2;
+  }
+  const size_t buf = lp_align(n_img * 64 * (size_t)H * W * sizeof(float));
+  P.off_b = buf;
+  P.off_partials = 2 * buf;
+  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -455,6 +739,98 @@ int dgs_lpips_alex(const float* a, const float* b, int32_t n_pairs, int32_t W, i
   hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_alex (finish)");
+}
+
+int dgs_conv3x3_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
+                          const float* bias, int32_t Cout, int32_t zscore, float* out, dgs_stream_t stream) {
+  if (in == nullptr || weight == nullptr || bias == nullptr || out == nullptr) return dgs_fail_arg("conv3x3_bias_relu: null pointer");
+  if (n_img < 1 || Cin < 1 || Cout < 1 || IH < 1 || IW < 1) return dgs_fail_arg("conv3x3_bias_relu: empty input or output");
+  if (zscore != 0 && (zscore != 1 || Cin != 3)) return dgs_fail_arg("conv3x3_bias_relu: zscore is 0 or 1, and 1 needs Cin = 3");
+  if ((int64_t)Cin * IH * IW >= (1ll << 31) || (int64_t)Cout * IH * IW >= (1ll << 31) || (int64_t)Cin * 9 >= (1ll << 23) ||
+      (int64_t)n_img * IH * IW >= (1ll << 31) || conv3x3_tiles(n_img, IH, IW) >= ((size_t)1 << 31) || Cout > 65535 * 64)
+    return dgs_fail_arg("conv3x3_bias_relu: sizes beyond the kernel's 32-bit index arithmetic");
+  ConvArgs g;
+  g.in0 = in;
+  g.in1 = in;
+  g.n_half = n_img;
+  g.w = weight;
+  g.bias = bias;
+  g.out = out;
+  g.Cin = Cin, g.IH = IH, g.IW = IW, g.Cout = Cout, g.OH = IH, g.OW = IW;
+  g.KH = 3, g.KW = 3, g.stride = 1, g.pad = 1, g.K = Cin * 9, g.N = n_img * IH * IW;
+  const hipError_t e = launch_conv3x3(g, n_img, zscore != 0, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "conv3x3_bias_relu");
+}
+
+int dgs_maxpool2x2(const float* in, uint64_t planes, int32_t IH, int32_t IW, float* out, dgs_stream_t stream) {
+  if (in == nullptr || out == nullptr) return dgs_fail_arg("maxpool2x2: null pointer");
+  if (planes < 1 || IH < 2 || IW < 2) return dgs_fail_arg("maxpool2x2: no planes, or planes below 2 x 2");
+  if ((int64_t)IH * IW >= (1ll << 31) || planes >= (1ull << 40)) return dgs_fail_arg("maxpool2x2: sizes beyond the kernel's index arithmetic");
+  const hipError_t e = launch_maxpool2x2(in, (size_t)planes, IH, IW, out, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "maxpool2x2");
+}
+
+size_t dgs_lpips_vgg_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
+  VggPlan P;
+  return vgg_plan(W, H, n_pairs, P) ? P.total_bytes : 0;
+}
+
+int dgs_lpips_vgg(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsVggWeights* w, void* tmp,
+                  float* out, dgs_stream_t stream) {
+  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr) return dgs_fail_arg("lpips_vgg: null pointer");
+  for (int l = 0; l < VGG_N; l++)
+    if (w->conv_w[l] == nullptr || w->conv_b[l] == nullptr)
+      return dgs_fail_arg("lpips_vgg: null pointer among the thirty-one weight pointers");
+  for (int t = 0; t < 5; t++)
+    if (w->lin[t] == nullptr) return dgs_fail_arg("lpips_vgg: null pointer among the thirty-one weight pointers");
+  if (n_pairs < 1) return dgs_fail_arg("lpips_vgg: n_pairs must be at least 1");
+  if (W < V_MIN || H < V_MIN) return dgs_fail_arg("lpips_vgg: the smallest image the network accepts is 16 x 16 (W and H >= 16)");
+  VggPlan P;
+  if (!vgg_plan(W, H, n_pairs, P)) return dgs_fail_arg("lpips_vgg: more than 65535 pairs or more pixels than one call covers");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(tmp);
+  float* bufs[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + P.off_b)};
+  double* partials = reinterpret_cast<double*>(base + P.off_partials);
+  const int n_img = 2 * n_pairs;
+
+  const float* cur = nullptr;   // the input of the next convolution (after the first: one array of n_img images)
+  int which = 0;                // the buffer the next kernel writes
+  int ih = H, iw = W, cin = 3;
+  for (int l = 0; l < VGG_N; l++) {
+    const int cout = VGG_COUT[l];
+    float* dst = bufs[which];
+    which ^= 1;
+    ConvArgs g;
+    g.in0 = (l == 0) ? a : cur;
+    g.in1 = (l == 0) ? b : cur + (size_t)n_pairs * cin * ih * iw;
+    g.n_half = n_pairs;
+    g.w = w->conv_w[l];
+    g.bias = w->conv_b[l];
+    g.out = dst;
+    g.Cin = cin, g.IH = ih, g.IW = iw, g.Cout = cout, g.OH = ih, g.OW = iw;
+    g.KH = 3, g.KW = 3, g.stride = 1, g.pad = 1, g.K = cin * 9, g.N = n_img * ih * iw;
+    hipError_t e = vgg_layer_on_conv3x3(cin, cout) ? launch_conv3x3(g, n_img, l == 0, s) : launch_conv(g, l == 0, s);
+    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_vgg (convolution)");
+    cur = dst;
+    cin = cout;
+    const int t = VGG_TAP[l];
+    if (t < 0) continue;
+    hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[t], (unsigned)n_pairs), dim3(256), 0, s, cur, (int)n_pairs,
+                       cout, ih * iw, w->lin[t], partials + P.taps.first[t]);
+    e = hipGetLastError();
+    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_vgg (layer distance)");
+    if (t < 4) {
+      float* pooled = bufs[which];
+      which ^= 1;
+      e = launch_maxpool2x2(cur, (size_t)n_img * cout, ih, iw, pooled, s);
+      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_vgg (max-pool)");
+      cur = pooled;
+      ih /= 2, iw /= 2;
+    }
+  }
+  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_vgg (finish)");
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 """Drop-in shim for the reference's `lpipsPyTorch` package: with `deblurgs_amd/dropin` on PYTHONPATH ahead of the
-reference's own directory, test.py's `from lpipsPyTorch import lpips` resolves to the MI355X operator (dgs_lpips_alex).
-The weights are those of deblurgs_amd.lpips.set_default_weights(...), else the two files a user of torchvision and of the
-LPIPS package already has under torch.hub.get_dir()/checkpoints (alexnet-owt-*.pth, alex.pth).  Only local files are
-opened: nothing is ever fetched.  See INTEGRATION.md."""
+reference's own directory, test.py's and metrics.py's `from lpipsPyTorch import lpips` resolve to the MI355X operators
+(dgs_lpips_alex, dgs_lpips_vgg).  The weights are those of deblurgs_amd.lpips.set_default_weights(...), else the two files
+a user of torchvision and of the LPIPS package already has under torch.hub.get_dir()/checkpoints (alexnet-owt-*.pth and
+alex.pth; vgg16-*.pth and vgg.pth).  Only local files are opened: nothing is ever fetched.  See INTEGRATION.md."""
 import torch
 
 from deblurgs_amd import lpips as _lpips
@@ -11,7 +11,17 @@ from deblurgs_amd import lpips as _lpips
 def lpips(x: torch.Tensor, y: torch.Tensor, net_type: str = 'alex', version: str = '0.1'):
     """The reference's signature and result (lpipsPyTorch/__init__.py:6-21): [3,H,W] or [N,3,H,W] in, one [1,1,1,1]
     tensor out, summed over the layers and over the batch."""
-    if net_type != 'alex':
-        raise NotImplementedError(f"deblurgs_amd implements LPIPS with the 'alex' backbone only (got {net_type!r})")
+    if net_type not in ('alex', 'vgg'):
+        raise NotImplementedError(f"deblurgs_amd implements LPIPS with the 'alex' and 'vgg' backbones only (got {net_type!r})")
     assert version in ['0.1'], 'v0.1 is only supported now'
+    if net_type == 'vgg':
+        try:
+            w = _lpips.default_weights(x.device, 'vgg')
+        except FileNotFoundError as e:
+            raise NotImplementedError(
+                "deblurgs_amd evaluates LPIPS with the 'vgg' backbone once its weights are there: torchvision's vgg16-*.pth and "
+                "the LPIPS v0.1 vgg.pth under torch.hub.get_dir()/checkpoints, or "
+                "deblurgs_amd.lpips.set_default_weights(LPIPSVggWeights.load(backbone_path, lin_path)).  Without them only "
+                "'alex' is evaluated.") from e
+        return _lpips.lpips(x, y, w)
     return _lpips.lpips(x, y, _lpips.default_weights(x.device))

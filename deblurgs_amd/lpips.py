@@ -1,4 +1,5 @@
-"""LPIPS with the AlexNet backbone, the third number of the reference's evaluation (test.py:120:
+"""LPIPS with the AlexNet backbone (below) and with the VGG16 backbone (further below: what metrics.py:74 reports).
+AlexNet: the third number of the reference's evaluation (test.py:120:
 `lpips(image, gt_image, net_type='alex')`, lpipsPyTorch/modules/{lpips,networks,utils}.py):
 
     z-score per channel   (x - (-.030, -.088, -.188)) / (.458, .448, .450), BEFORE the first convolution, so the
@@ -19,6 +20,13 @@ state dicts a user already has (torchvision's AlexNet and the published LPIPS v0
 dgs_lpips_alex (csrc/lpips.hip: an implicit-GEMM convolution on the f32 matrix cores, a max-pool and a layer-distance
 kernel; no MIOpen, no host synchronisation); anything else (CPU, fp64) runs the torch expressions below.
 tests/golden/lpips_golden.npz pins both paths against the reference's own module.
+
+VGG16 (`net_type='vgg'`, networks.py:88-96): the same z-score, thirteen conv 3x3 pad 1 each with a ReLU, max-pool 2x2 /2
+after convolutions 2, 4, 7 and 10; taps after convolutions 2, 4, 7, 10 (before the pool) and 13 -- torchvision's
+`features` modules 4, 9, 16, 23, 30 counted from 1; the smallest image is 16 x 16.  `LPIPSVggWeights` takes torchvision's
+VGG16 state dict and the published `vgg.pth`; fp32 device inputs run dgs_lpips_vgg (csrc/lpips.hip: conv3x3_kernel reads
+its operands from an input halo tile in LDS).  Which backbone a call runs is the weights' `net_type`.
+tests/golden/lpips_vgg_golden.npz pins both paths.
 """
 import ctypes
 import glob
@@ -37,6 +45,14 @@ CONVS = ((64, 3, 11, 4, 2, True), (192, 64, 5, 1, 2, True), (384, 192, 3, 1, 1, 
 FEATURE_INDEX = (0, 3, 6, 8, 10)
 CHANNELS = tuple(c[0] for c in CONVS)
 MIN_SIZE = 31
+# VGG16: Cout of the thirteen convolutions, their index in torchvision's `features`, the tap each one feeds (or None)
+VGG_COUT = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+VGG_CIN = (3,) + VGG_COUT[:-1]
+VGG_FEATURE_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
+VGG_TAP = (None, 0, None, 1, None, None, 2, None, None, 3, None, None, 4)
+VGG_CHANNELS = (64, 128, 256, 512, 512)
+VGG_MIN_SIZE = 16
+MAX_TMP_BYTES = 4 << 30
 
 
 def _pick(sd, names, what):
@@ -55,6 +71,8 @@ def _as_f32(name, t, shape):
 
 class LPIPSWeights:
     """The fifteen tensors of LPIPS-alex: `conv_w[i]` [Cout,Cin,k,k], `conv_b[i]` [Cout], `lin[i]` [1,C,1,1]."""
+    net_type = "alex"
+    min_size = MIN_SIZE
 
     def __init__(self, conv_w, conv_b, lin):
         self.conv_w, self.conv_b, self.lin = list(conv_w), list(conv_b), list(lin)
@@ -102,21 +120,81 @@ class LPIPSWeights:
         return self._struct
 
 
-def _batched(x, y):
+class LPIPSVggWeights:
+    """The thirty-one tensors of LPIPS-vgg: `conv_w[i]` [Cout,Cin,3,3], `conv_b[i]` [Cout] (13 each), `lin[i]` [1,C,1,1]."""
+    net_type = "vgg"
+    min_size = VGG_MIN_SIZE
+
+    def __init__(self, conv_w, conv_b, lin):
+        self.conv_w, self.conv_b, self.lin = list(conv_w), list(conv_b), list(lin)
+        self._struct = None
+
+    @classmethod
+    def from_state_dicts(cls, features_sd, lin_sd):
+        """features_sd: torchvision's VGG16 state dict (`features.{0,2,5,...,28}.{weight,bias}`) or that of its `.features`
+        alone; lin_sd: the published `lin{i}.model.1.weight` of vgg.pth, or the reference's renamed `{i}.1.weight`.  A
+        missing key or a wrong shape raises with the key named."""
+        conv_w, conv_b, lin = [], [], []
+        for idx, co, ci in zip(VGG_FEATURE_INDEX, VGG_COUT, VGG_CIN):
+            for part, shape, dst in (("weight", (co, ci, 3, 3), conv_w), ("bias", (co,), conv_b)):
+                name, t = _pick(features_sd, (f"features.{idx}.{part}", f"{idx}.{part}"), f"features.{idx}.{part}")
+                dst.append(_as_f32(name, t, shape))
+        for i, c in enumerate(VGG_CHANNELS):
+            name, t = _pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight")
+            lin.append(_as_f32(name, t, (1, c, 1, 1)))
+        return cls(conv_w, conv_b, lin)
+
+    @classmethod
+    def load(cls, backbone_path, lin_path):
+        """The two local checkpoint files (torch.load on the CPU, tensors only)."""
+        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu", weights_only=True),
+                                    torch.load(lin_path, map_location="cpu", weights_only=True))
+
+    def tensors(self):
+        return self.conv_w + self.conv_b + self.lin
+
+    @property
+    def device(self):
+        return self.conv_w[0].device
+
+    def to(self, device):
+        mv = lambda ts: [t.to(device) for t in ts]
+        return LPIPSVggWeights(mv(self.conv_w), mv(self.conv_b), mv(self.lin))
+
+    def struct(self):
+        """The DgsLpipsVggWeights of these tensors (they stay alive with this object)."""
+        if self._struct is None:
+            s = _lib.DgsLpipsVggWeights()
+            for i in range(13):
+                s.conv_w[i], s.conv_b[i] = self.conv_w[i].data_ptr(), self.conv_b[i].data_ptr()
+            for i in range(5):
+                s.lin[i] = self.lin[i].data_ptr()
+            self._struct = s
+        return self._struct
+
+
+def _batched(x, y, min_size=MIN_SIZE):
     if x.shape != y.shape or x.dim() not in (3, 4) or x.shape[-3] != 3:
         raise ValueError(f"lpips takes two [3,H,W] or [N,3,H,W] tensors of one shape (got {tuple(x.shape)}, {tuple(y.shape)})")
     if x.dim() == 3:
         x, y = x[None], y[None]
-    if x.shape[-1] < MIN_SIZE or x.shape[-2] < MIN_SIZE:
-        raise ValueError(f"lpips needs images of at least {MIN_SIZE} x {MIN_SIZE} pixels (got {x.shape[-2]} x {x.shape[-1]})")
+    if x.shape[-1] < min_size or x.shape[-2] < min_size:
+        raise ValueError(f"lpips needs images of at least {min_size} x {min_size} pixels (got {x.shape[-2]} x {x.shape[-1]})")
     return x, y
-
 
 def _features_torch(x, w):
     """The five normalised taps of x [N,3,H,W] (networks.py:53-66) in x's dtype on x's device."""
     t = lambda a: a.to(device=x.device, dtype=x.dtype)
     x = (x - t(torch.tensor(MEAN))[None, :, None, None]) / t(torch.tensor(STD))[None, :, None, None]
     out = []
+    if w.net_type == "vgg":                                 # networks.py:88-96
+        for i, tap in enumerate(VGG_TAP):
+            x = F.relu(F.conv2d(x, t(w.conv_w[i]), t(w.conv_b[i]), stride=1, padding=1))
+            if tap is not None:
+                out.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10))
+                if tap < 4:
+                    x = F.max_pool2d(x, kernel_size=2, stride=2)
+        return out
     for i, (_, _, _, stride, pad, pool) in enumerate(CONVS):
         x = F.relu(F.conv2d(x, t(w.conv_w[i]), t(w.conv_b[i]), stride=stride, padding=pad))
         out.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10))
@@ -136,11 +214,13 @@ def _fused_ok(x, y):
     return (x.device.type == "cuda" and y.device == x.device and x.dtype == torch.float32 and y.dtype == torch.float32)
 
 
-def lpips_layers(x, y, weights):
-    """[N,6] = (total, layer 1..5) per pair of x, y ([3,H,W] or [N,3,H,W]).  fp32 device inputs: one dgs_lpips_alex call
-    on the current stream (the weights must live on that device), no host synchronisation; otherwise the torch
-    expressions in the inputs' dtype."""
-    x, y = _batched(x, y)
+def lpips_layers(x, y, weights, max_tmp_bytes=MAX_TMP_BYTES):
+    """[N,6] = (total, layer 1..5) per pair of x, y ([3,H,W] or [N,3,H,W]) with the backbone of `weights` (LPIPSWeights:
+    alex, LPIPSVggWeights: vgg).  fp32 device inputs: dgs_lpips_alex / dgs_lpips_vgg on the current stream (the weights
+    must live on that device), no host synchronisation; otherwise the torch expressions in the inputs' dtype.  A vgg batch
+    whose scratch would pass max_tmp_bytes is cut into consecutive calls: a pair's numbers do not depend on the other
+    pairs of its call, so the result is the same bit for bit."""
+    x, y = _batched(x, y, weights.min_size)
     if not _fused_ok(x, y):
         return _layers_torch(x, y, weights)
     if weights.device != x.device:
@@ -148,9 +228,19 @@ def lpips_layers(x, y, weights):
     x, y = x.contiguous(), y.contiguous()
     L = _lib.lib()
     N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    tmp = torch.empty(L.dgs_lpips_alex_tmp_bytes(W, H, N), dtype=torch.uint8, device=x.device)
     out = torch.empty((N, 6), dtype=torch.float32, device=x.device)
     st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    if weights.net_type == "vgg":
+        per_call = N
+        while per_call > 1 and L.dgs_lpips_vgg_tmp_bytes(W, H, per_call) > max_tmp_bytes:
+            per_call = (per_call + 1) // 2
+        tmp = torch.empty(L.dgs_lpips_vgg_tmp_bytes(W, H, per_call), dtype=torch.uint8, device=x.device)
+        for i in range(0, N, per_call):
+            n = min(per_call, N - i)
+            _lib.check(L.dgs_lpips_vgg(x[i:i + n].data_ptr(), y[i:i + n].data_ptr(), n, W, H, ctypes.byref(weights.struct()),
+                                       tmp.data_ptr(), out[i:i + n].data_ptr(), st), "dgs_lpips_vgg")
+        return out
+    tmp = torch.empty(L.dgs_lpips_alex_tmp_bytes(W, H, N), dtype=torch.uint8, device=x.device)
     _lib.check(L.dgs_lpips_alex(x.data_ptr(), y.data_ptr(), N, W, H, ctypes.byref(weights.struct()), tmp.data_ptr(),
                                 out.data_ptr(), st), "dgs_lpips_alex")
     return out
@@ -175,6 +265,36 @@ def conv2d_bias_relu(x, weight, bias, stride=1, padding=0, zscore=False):
     return out
 
 
+def conv3x3_bias_relu(x, weight, bias, zscore=False):
+    """relu(conv2d(x, weight, bias, stride 1, padding 1)), weight [Cout,Cin,3,3], through dgs_conv3x3_bias_relu, the
+    halo-tile convolution kernel of dgs_lpips_vgg on its own.  No fallback."""
+    if not (_fused_ok(x, weight) and _fused_ok(x, bias)) or x.dim() != 4 or weight.dim() != 4:
+        raise RuntimeError("conv3x3_bias_relu needs float32 tensors on one HIP device: x [N,Cin,H,W], weight [Cout,Cin,3,3]")
+    x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
+    N, Cin, IH, IW = (int(v) for v in x.shape)
+    Cout = int(weight.shape[0])
+    if tuple(weight.shape) != (Cout, Cin, 3, 3) or tuple(bias.shape) != (Cout,):
+        raise ValueError("conv3x3_bias_relu: weight is [Cout,Cin,3,3] and bias [Cout]")
+    out = torch.empty((N, Cout, IH, IW), dtype=torch.float32, device=x.device)
+    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.lib().dgs_conv3x3_bias_relu(x.data_ptr(), N, Cin, IH, IW, weight.data_ptr(), bias.data_ptr(), Cout,
+                                                int(bool(zscore)), out.data_ptr(), st), "dgs_conv3x3_bias_relu")
+    return out
+
+
+def maxpool2x2(x):
+    """max_pool2d(x, 2, 2) of a float32 device tensor [..., H, W] through dgs_maxpool2x2.  No fallback."""
+    if not _fused_ok(x, x) or x.dim() < 2:
+        raise RuntimeError("maxpool2x2 needs a float32 tensor [..., H, W] on a HIP device")
+    x = x.contiguous()
+    IH, IW = int(x.shape[-2]), int(x.shape[-1])
+    planes = x.numel() // max(IH * IW, 1)
+    out = torch.empty(tuple(x.shape[:-2]) + (IH // 2, IW // 2), dtype=torch.float32, device=x.device)
+    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.lib().dgs_maxpool2x2(x.data_ptr(), planes, IH, IW, out.data_ptr(), st), "dgs_maxpool2x2")
+    return out
+
+
 def lpips(x, y, weights):
     """The reference's criterion (lpips.py:28-36): [3,H,W] or [N,3,H,W] in, ONE [1,1,1,1] tensor out -- the sum over the
     five layers and over the batch."""
@@ -182,35 +302,44 @@ def lpips(x, y, weights):
 
 
 # ---- the weights the drop-in `lpipsPyTorch.lpips` uses
-_default = {}
+_default = {"alex": {}, "vgg": {}}
+# per backbone: the class, torchvision's checkpoint (a glob), the LPIPS v0.1 linear layers
+_FILES = {"alex": (LPIPSWeights, "alexnet-owt-*.pth", "alex.pth"), "vgg": (LPIPSVggWeights, "vgg16-*.pth", "vgg.pth")}
 
 
 def set_default_weights(weights):
-    """The weights `deblurgs_amd/dropin/lpipsPyTorch` evaluates with (None: forget them)."""
-    _default.clear()
-    if weights is not None:
-        _default[weights.device] = weights
+    """The weights `deblurgs_amd/dropin/lpipsPyTorch` evaluates with, filed under their net_type (None: forget them all)."""
+    if weights is None:
+        for d in _default.values():
+            d.clear()
+        return
+    _default[weights.net_type].clear()
+    _default[weights.net_type][weights.device] = weights
 
 
-def default_weights(device):
-    """The default weights on `device`: those of set_default_weights, else the two files a user of torchvision and of the
-    LPIPS package already has in torch.hub's checkpoint directory.  Only local files are opened; nothing is fetched."""
+def default_weights(device, net_type="alex"):
+    """The default weights of a backbone on `device`: those of set_default_weights, else the two files a user of
+    torchvision and of the LPIPS package already has in torch.hub's checkpoint directory.  Only local files are opened;
+    nothing is fetched."""
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    if device in _default:
-        return _default[device]
-    if _default:
-        w = next(iter(_default.values())).to(device)
+    have = _default[net_type]
+    if device in have:
+        return have[device]
+    if have:
+        w = next(iter(have.values())).to(device)
     else:
+        cls, backbone_glob, lin_name = _FILES[net_type]
         ckpt = os.path.join(torch.hub.get_dir(), "checkpoints")
-        backbone = sorted(glob.glob(os.path.join(ckpt, "alexnet-owt-*.pth")))
-        lin = os.path.join(ckpt, "alex.pth")
+        backbone = sorted(glob.glob(os.path.join(ckpt, backbone_glob)))
+        lin = os.path.join(ckpt, lin_name)
         if not backbone or not os.path.exists(lin):
             raise FileNotFoundError(
-                f"LPIPS needs two weight files and neither ships with this package: torchvision's AlexNet checkpoint "
-                f"(alexnet-owt-*.pth) and the LPIPS v0.1 linear layers (alex.pth).  Put both into {ckpt}, or call "
-                "deblurgs_amd.lpips.set_default_weights(LPIPSWeights.load(backbone_path, lin_path)).")
-        w = LPIPSWeights.load(backbone[-1], lin).to(device)
-    _default[device] = w
+                f"LPIPS needs two weight files and neither ships with this package: torchvision's "
+                f"{'AlexNet' if net_type == 'alex' else 'VGG16'} checkpoint ({backbone_glob}) and the LPIPS v0.1 linear layers "
+                f"({lin_name}).  Put both into {ckpt}, or call "
+                f"deblurgs_amd.lpips.set_default_weights({cls.__name__}.load(backbone_path, lin_path)).")
+        w = cls.load(backbone[-1], lin).to(device)
+    have[device] = w
     return w

@@ -694,6 +694,44 @@ int dgs_conv2d_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH
                          const float* bias, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t zscore,
                          float* out, dgs_stream_t stream);
 
+/* ---- LPIPS with the VGG16 backbone (additions to ABI 15; metrics.py:74, networks.py:88-96 of the reference) ----
+ * lpips(x, y, net_type='vgg'), again with CALLER-SUPPLIED weights.  torchvision's VGG16 `features` shapes:
+ *   conv_w[0..12]  [Cout,Cin,3,3], Cout = 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512, Cin = 3 and then
+ *                  the Cout before                                 (features.0/2/5/7/10/12/14/17/19/21/24/26/28)
+ *   conv_b[0..12]  [Cout]
+ *   lin[0..4]      [1,C,1,1], C = 64, 128, 256, 512, 512           (LPIPS v0.1 lin{i}.model.1.weight of vgg.pth)
+ * all fp32, contiguous, in device memory. */
+typedef struct DgsLpipsVggWeights {
+  const float* conv_w[13];
+  const float* conv_b[13];
+  const float* lin[5];
+} DgsLpipsVggWeights;
+/* As dgs_lpips_alex, with the network z-score, then thirteen conv 3x3 pad 1 each with a ReLU, a max-pool 2x2 /2 (floor)
+ * after convolutions 2, 4, 7 and 10; taps: the ReLU outputs of convolutions 2, 4, 7, 10 (each before its pool) and 13.
+ * out [n_pairs,6] = per pair (total, layer 1..5).  Every contract of dgs_lpips_alex holds: stream-explicit, caller-owned
+ * memory, no host synchronisation, no float atomics, a pair's six numbers independent of the other pairs and of n_pairs,
+ * two runs bitwise equal, lpips(x, x) exactly 0 and lpips(x, y) == lpips(y, x) bitwise.
+ * tmp >= dgs_lpips_vgg_tmp_bytes(W, H, n_pairs) bytes (0: arguments the call refuses), 256-byte aligned: two ping-pong
+ * buffers of the largest layer output [2 n_pairs,64,H,W] and the distance partials -- 2,123,452,928 bytes for one
+ * 1920 x 1080 pair.  Refused before any HIP call: a NULL pointer (the thirty-one of `w` included), n_pairs < 1 (or above
+ * 65535), W or H below 16 -- the smallest image the network accepts, as the reference raises at 15 -- and 64 H W or
+ * 2 n_pairs H W of 2^31 and more. */
+size_t dgs_lpips_vgg_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs);
+int dgs_lpips_vgg(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsVggWeights* w,
+                  void* tmp, float* out, dgs_stream_t stream);
+/* The 3 x 3 convolution of the above on its own: out [n_img,Cout,IH,IW] = relu(conv2d(in [n_img,Cin,IH,IW], weight
+ * [Cout,Cin,3,3], bias [Cout], stride 1, zero padding 1)) on v_mfma_f32_32x32x2_f32, the operands read from an input halo
+ * tile in LDS (no patch gather).  Every output element is: per chunk of CC input channels (CC = 4 where Cout <= 64, else
+ * 8) one fmaf chain of L = 9 CC terms (36 / 72) from 0 in the k order (ky, kx, ci) -- for each of the nine weights in
+ * row-major order the chunk's channels in order, a term past Cin being 0 x 0 --, the chunks' results added in channel
+ * order with a compensated (Kahan) fp32 sum, + bias, ReLU (a NaN passes) -- whatever its place in the call.  zscore = 1 (Cin = 3): as dgs_conv2d_bias_relu's.  `out` must not
+ * overlap `in`. */
+int dgs_conv3x3_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
+                          const float* bias, int32_t Cout, int32_t zscore, float* out, dgs_stream_t stream);
+/* max_pool2d(kernel 2, stride 2) of `planes` planes [IH,IW] -> [IH / 2, IW / 2] (floor, no padding; IH, IW >= 2); a NaN in
+ * a window is its result.  `out` must not overlap `in`. */
+int dgs_maxpool2x2(const float* in, uint64_t planes, int32_t IH, int32_t IW, float* out, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
