@@ -98,6 +98,16 @@ class DgsLpipsVggWeights(ctypes.Structure):
     _fields_ = [("conv_w", ctypes.c_void_p * 13), ("conv_b", ctypes.c_void_p * 13), ("lin", ctypes.c_void_p * 5)]
 
 
+class DgsFireWeights(ctypes.Structure):
+    _fields_ = [("squeeze_w", ctypes.c_void_p), ("squeeze_b", ctypes.c_void_p), ("expand1_w", ctypes.c_void_p),
+                ("expand1_b", ctypes.c_void_p), ("expand3_w", ctypes.c_void_p), ("expand3_b", ctypes.c_void_p)]
+
+
+class DgsLpipsSqueezeWeights(ctypes.Structure):
+    _fields_ = [("conv_w", ctypes.c_void_p), ("conv_b", ctypes.c_void_p), ("fire", DgsFireWeights * 8),
+                ("lin", ctypes.c_void_p * 7)]
+
+
 ADAM_MAX_GROUPS = 16
 ABI_VERSION = 15           # DGS_ABI_VERSION of include/dgs_hip.h (tests/test_abi.py keeps the two in step)
 
@@ -234,6 +244,13 @@ EXPORTS = {
     "dgs_conv3x3_bias_relu": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2 +
                               [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2),
     "dgs_maxpool2x2": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 2),
+    "dgs_lpips_squeeze_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
+    "dgs_lpips_squeeze": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 3 + [ctypes.POINTER(DgsLpipsSqueezeWeights)] +
+                          [ctypes.c_void_p] * 3),
+    "dgs_fire_bias_relu": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 7 + [ctypes.POINTER(DgsFireWeights)] +
+                           [ctypes.c_void_p] * 3),
+    "dgs_maxpool3x3s2_ceil": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32] +
+                              [ctypes.c_void_p] * 2),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

@@ -1,12 +1,15 @@
 // lpips.hip -- LPIPS with the AlexNet backbone, the third number of the reference's evaluation (test.py:120,
-// lpipsPyTorch/modules/{lpips,networks,utils}.py), and with the VGG16 backbone, the one metrics.py:74 reports, with
-// caller-supplied weights:
+// lpipsPyTorch/modules/{lpips,networks,utils}.py), with the VGG16 backbone, the one metrics.py:74 reports, and with
+// SqueezeNet 1.1, all with caller-supplied weights:
 //   * conv_kernel: ONE implicit-GEMM fp32 convolution for all five layers on the f32-input matrix cores
 //     (v_mfma_f32_32x32x2_f32), with bias + ReLU in the epilogue and the z-score of the input fused into the first
 //     layer's gather;
 //   * maxpool_kernel: 3 x 3 stride 2, floor, no padding;
 //   * conv3x3_kernel: VGG's 3 x 3 / stride 1 / pad 1 convolutions from an input halo tile in LDS, on the same matrix
 //     cores with the same epilogue; maxpool2x2_kernel: VGG's 2 x 2 stride 2 pool;
+//   * fire_kernel: a SqueezeNet Fire module (squeeze 1 x 1, expand 1 x 1 and 3 x 3, concatenated) in ONE launch, the
+//     squeeze map of a tile and its halo kept in LDS; maxpool3x3s2_ceil_kernel: SqueezeNet's ceil-mode pool
+//     (net_type='squeeze', networks.py:69-77);
 //   * layer_distance_kernel + lpips_finish_kernel: per tap the channel-normalised squared difference under the "lin"
 //     weights, reduced over space in block order.
 // Built with -ffp-contract=off (deblurgs_amd/build.py): the compensated sum of the convolution below is only what it says
@@ -431,6 +434,351 @@ maxpool2x2_kernel(const float* __restrict__ in, float* __restrict__ out, size_t 
   }
 }
 
+// ---- SqueezeNet 1.1: a Fire module in one launch, and the ceil-mode pool
+constexpr int F_S_MAX = 64;                      // deepest squeeze map the kernel holds in LDS
+constexpr int F_BM = 64;                         // expand channels of a stage-2 slab
+constexpr int F_CC = 8;                          // squeeze channels per 3 x 3 weight chunk
+constexpr int F_WP = F_BM + 1;                   // pitch of the staged expand weights
+constexpr int F_WROWS = 9 * F_CC;                // k rows of a staged expand-weight chunk (72; the 1 x 1 slab uses <= 64)
+constexpr int F_NT = (V_CH + 31) / 32;           // 32-pixel MFMA column tiles that cover the 204 halo pixels: 7
+constexpr int Q_MIN = 17;                        // smallest image: 8 x 8 after the first convolution, pools to 4, 2, 1
+
+struct FireArgs {
+  const float* in0;     // images [0, n_half) [n_half,Cin,IH,IW]
+  const float* in1;     // images [n_half, n_img)
+  int n_half;
+  const float *sw, *sb; // squeeze [S,Cin], [S]
+  const float *w1, *b1; // expand 1 x 1 [E1,S], [E1]
+  const float *w3, *b3; // expand 3 x 3 [E3,S,3,3], [E3]
+  float* sq_out;        // [n_img,S,IH,IW] or nullptr
+  float* out;           // [n_img,E1+E3,IH,IW]
+  int Cin, IH, IW, S, E1, E3, tiles_x, tiles_per_img;
+};
+
+// out = cat(relu(conv1x1(s, w1, b1)), relu(conv3x3(s, w3, b3, pad 1))), s = relu(conv1x1(in, sw, sb)): a block owns 4 rows x 32
+// columns of ONE image (conv3x3_kernel's tile) and the expand slabs j = blockIdx.y, blockIdx.y + gridDim.y, ... (slab j:
+// channels [64 j, 64 j + 64) of BOTH expands, so blocks of one grid row carry equal work when E1 = E3).
+// Stage 1: the squeeze map of the tile and its 1-pixel halo, S x 204 values, as C[S x 204] = sw[S x Cin] . in[Cin x 204]
+// on v_mfma_f32_32x32x2_f32: MT = 1 (S <= 32) or 2 row tiles of 32 squeeze channels by seven column tiles of 32 halo
+// pixels (the halo in its dense [row][34] order; columns 204 .. 223 of the seventh are computed and dropped), wave w the
+// column tiles w and w + 4.  The input goes through LDS in chunks of CK channels (s_in[k][204], zeros outside the image
+// and past Cin: conv3x3_kernel's staging, double-buffered, one barrier per chunk) with the matching columns of sw
+// transposed (s_w1[k][m]).  With bias and ReLU the map is written to s_sq[m][204] -- conv3x3_kernel's s_h with the whole
+// squeeze depth as its one chunk -- and never to HBM (sq_out, for the tests: each element once, by the block whose
+// interior holds it, grid row 0).  A halo position OUTSIDE the image holds 0, not relu(bias): the 3 x 3 expand's zero
+// padding pads the squeeze output.  Rows S .. 32 MT - 1 hold 0.  A halo pixel is recomputed by up to four blocks: its
+// value is the same chain whichever column of whichever tile holds it.
+// Stage 2: per slab the 1 x 1 expand (weights s_w2[ci][m], B operand s_sq[ci][row + 1][1 + 32 columns]) and the 3 x 3
+// expand in chunks of 8 squeeze channels (weights s_w2[(ky, kx)][ci][m], B operand s_sq[c0 + ci][row + ky][kx + 32
+// columns]: conv3x3_kernel's reads); wave w makes row w of the tile, 64 channels = two MFMA row tiles.  The expand weights
+// are double-buffered in the LDS the stage-1 staging has left, loaded into registers one item ahead, one barrier per item.
+// Results go to channels [0, E1) and [E1, E1 + E3) of `out`: no concatenation pass.
+// All ds_read_b32 / ds_write_b32 touch 32 consecutive floats per lane group: conflict-free (s_w1's transposed write: pitch
+// 65 at CK = 32, 34 at CK = 16: the 32 lanes of a group fall on 32 banks).
+// LDS: MT = 2, CK = 32: s_sq 52 224 B + staging 69 120 B = 121 344 B; MT = 1, CK = 16: 26 112 B + 37 440 B = 63 552 B.
+// Both instantiations run at one wave per SIMD (the compiler takes more than 256 registers; held to 256 the MT = 1
+// instantiation spills 129), so a CU holds one block of either.
+// Numerics, fp32 throughout.  Stage 1: per chunk of CK input channels (CK = 16 where S <= 32, else 32) one fmaf chain of
+// L1 = CK terms from 0 in channel order (terms past Cin are 0 x 0); the chunks' sums are added in channel order with
+// conv_kernel's compensated sum; then bias, then ReLU (a NaN passes).  Stage 2, 1 x 1 expand: ONE fmaf chain of
+// L2a = S terms from 0 in channel order (S + 1 for odd S: a last 0 x 0), then bias, then ReLU.  Stage 2, 3 x 3 expand: per
+// chunk of 8 squeeze channels one chain of L2b = 72 terms from 0 in the k order (ky, kx, ci) -- conv3x3_kernel's --, the
+// chunks' sums added in channel order with the compensated sum, then bias, then ReLU.  An element's arithmetic depends on
+// the layer shape and the image size only, never on n_img, the image's place in the call, the pixel's place in a tile,
+// or the number of grid rows.
+template <int MT, int CK>
+__global__ void __launch_bounds__(256) fire_kernel(const FireArgs g) {
+  constexpr int BM1 = MT * 32, P1 = BM1 + (CK == 32 ? 1 : 2);
+  constexpr int IN_FLOATS = CK * V_CH + 32;      // + 32: the seventh column tile reads 20 floats past the last channel
+  constexpr int NH = (CK * V_CH + 255) / 256, NW1 = BM1 * CK / 256, NW2 = F_BM * F_WROWS / 256;
+  constexpr int STAGE1 = 2 * IN_FLOATS + 2 * CK * P1, STAGE2 = 2 * F_WROWS * F_WP;
+  static_assert((BM1 * CK) % 256 == 0 && (F_BM * F_WROWS) % 256 == 0 && BM1 >= F_CC, "staging loops");
+  __shared__ float s_sq[BM1 * V_CH];
+  __shared__ float s_stage[STAGE1 > STAGE2 ? STAGE1 : STAGE2];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, lh = lane >> 5;
+  const int img = blockIdx.x / g.tiles_per_img, tile = blockIdx.x - img * g.tiles_per_img;
+  const int ty = tile / g.tiles_x;
+  const int y0 = ty * V_ROWS, x0 = (tile - ty * g.tiles_x) * V_COLS;
+  const int ihw = g.IH * g.IW;
+  const float* src = (img < g.n_half) ? g.in0 + (size_t)img * g.Cin * ihw : g.in1 + (size_t)(img - g.n_half) * g.Cin * ihw;
+
+  // ---- stage 1
+  {
+    float* s_in = s_stage;                       // [2][IN_FLOATS]
+    float* s_w1 = s_stage + 2 * IN_FLOATS;       // [2][CK * P1]
+    int h_off[NH];                               // < 0: outside the image (or past the halo's end): stays 0
+#pragma unroll
+    for (int i = 0; i < NH; i++) {
+      const int e = t + 256 * i;
+      const int ci = e / V_CH, rem = e - ci * V_CH;
+      const int r = rem / V_PITCH, c = rem - r * V_PITCH;
+      const int iy = y0 - 1 + r, ix = x0 - 1 + c;
+      const bool in = e < CK * V_CH && (unsigned)iy < (unsigned)g.IH && (unsigned)ix < (unsigned)g.IW;
+      h_off[i] = in ? ci * ihw + iy * g.IW + ix : -1;
+    }
+    float rw[NW1], rh[NH];
+    auto load_chunk = [&](int c0) {
+#pragma unroll
+      for (int i = 0; i < NW1; i++) {            // CK consecutive floats of a squeeze-weight row per CK threads
+        const int e = t + 256 * i;
+        const int ml = e / CK, k = e - ml * CK;
+        rw[i] = (ml < g.S && c0 + k < g.Cin) ? g.sw[(size_t)ml * g.Cin + c0 + k] : 0.0f;
+      }
+#pragma unroll
+      for (int i = 0; i < NH; i++) {
+        const int ci = (t + 256 * i) / V_CH;
+        rh[i] = (h_off[i] >= 0 && c0 + ci < g.Cin) ? src[(size_t)c0 * ihw + h_off[i]] : 0.0f;
+      }
+    };
+    auto store_chunk = [&](int b) {
+#pragma unroll
+      for (int i = 0; i < NW1; i++) {
+        const int e = t + 256 * i;
+        const int ml = e / CK, k = e - ml * CK;
+        s_w1[b * CK * P1 + k * P1 + ml] = rw[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NH; i++)
+        if (t + 256 * i < CK * V_CH) s_in[b * IN_FLOATS + t + 256 * i] = rh[i];
+    };
+
+    const bool two = wave + 4 < F_NT;            // waves 0..2 own two column tiles, wave 3 one
+    f32x16 tot[MT][2], comp[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          tot[i][j][r] = 0.0f;
+          comp[i][j][r] = 0.0f;
+        }
+    const int n_chunks = (g.Cin + CK - 1) / CK;
+    load_chunk(0);
+    for (int c = 0; c < n_chunks; c++) {
+      const int b = c & 1;
+      store_chunk(b);
+      __syncthreads();
+      if (c + 1 < n_chunks) load_chunk((c + 1) * CK);
+      const float* wb = s_w1 + b * CK * P1 + lh * P1 + l31;
+      const float* hb = s_in + b * IN_FLOATS + lh * V_CH + wave * 32 + l31;
+      f32x16 acc[MT][2];
+#pragma unroll
+      for (int i = 0; i < MT; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+#pragma unroll
+      for (int kk = 0; kk < CK; kk += 2) {
+        float a[MT], bv[2];
+#pragma unroll
+        for (int i = 0; i < MT; i++) a[i] = wb[kk * P1 + i * 32];
+        bv[0] = hb[kk * V_CH];
+        bv[1] = two ? hb[kk * V_CH + 128] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < MT; i++) {
+          acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bv[0], acc[i][0], 0, 0, 0);
+          if (two) acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bv[1], acc[i][1], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < MT; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {  // Kahan, as conv_kernel
+          const f32x16 y = acc[i][j] - comp[i][j];
+          const f32x16 s = tot[i][j] + y;
+          comp[i][j] = (s - tot[i][j]) - y;
+          tot[i][j] = s;
+        }
+    }
+    // bias + ReLU into s_sq; C/D layout: column (halo pixel) = lane & 31, row (squeeze channel) = (r & 3) + 8 (r >> 2) +
+    // 4 (lane >> 5): per register a lane group writes 32 consecutive floats
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      const int hp = (wave + 4 * j) * 32 + l31;
+      if ((j == 1 && !two) || hp >= V_CH) continue;
+      const int hr = hp / V_PITCH, hc = hp - hr * V_PITCH;
+      const int iy = y0 - 1 + hr, ix = x0 - 1 + hc;
+      const bool in = (unsigned)iy < (unsigned)g.IH && (unsigned)ix < (unsigned)g.IW;
+      const bool mine = in && g.sq_out != nullptr && blockIdx.y == 0 && hr >= 1 && hr <= V_ROWS && hc >= 1 && hc <= V_COLS;
+#pragma unroll
+      for (int i = 0; i < MT; i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int m = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          float v = 0.0f;
+          if (in && m < g.S) {
+            v = tot[i][j][r] + g.sb[m];
+            v = (v < 0.0f) ? 0.0f : v;
+          }
+          s_sq[m * V_CH + hp] = v;
+          if (mine && m < g.S) g.sq_out[((size_t)img * g.S + m) * ihw + iy * g.IW + ix] = v;
+        }
+    }
+  }
+  __syncthreads();   // s_sq is complete, and every wave has left the stage-1 staging that the expand weights now overwrite
+
+  // ---- stage 2: items of this block in order: per slab j the 1 x 1 expand (p = 0, if 64 j < E1), then the chunks
+  // p = 1 .. nc of the 3 x 3 expand (if 64 j < E3)
+  const int n1 = (g.E1 + F_BM - 1) / F_BM, n3 = (g.E3 + F_BM - 1) / F_BM, nsl = n1 > n3 ? n1 : n3;
+  const int nc = (g.S + F_CC - 1) / F_CC, s_even = g.S + (g.S & 1);
+  const int step = gridDim.y;
+  auto advance = [&](int& j, int& p) {           // the next item (j >= nsl: none)
+    do {
+      if (p < nc) {
+        p++;
+      } else {
+        p = 0;
+        j += step;
+      }
+    } while (j < nsl && !(p == 0 ? j < n1 : j < n3));
+  };
+  float rw[NW2];
+  auto load_item = [&](int j, int p) {
+    const int m0 = j * F_BM;
+    if (p == 0) {   // [64, S] of w1 is one dense run: thread t takes floats t, t + 256, ...
+#pragma unroll
+      for (int i = 0; i < NW2; i++) {
+        const int e = t + 256 * i;
+        const int ml = e / g.S;
+        rw[i] = (e < F_BM * g.S && m0 + ml < g.E1) ? g.w1[(size_t)m0 * g.S + e] : 0.0f;
+      }
+    } else {        // 72 consecutive floats of the weight tensor per output channel (conv3x3_kernel's load)
+      const int c0 = (p - 1) * F_CC;
+#pragma unroll
+      for (int i = 0; i < NW2; i++) {
+        const int e = t + 256 * i;
+        const int ml = e / F_WROWS, r = e - ml * F_WROWS;
+        rw[i] = (m0 + ml < g.E3 && c0 + r / 9 < g.S) ? g.w3[((size_t)(m0 + ml) * g.S + c0) * 9 + r] : 0.0f;
+      }
+    }
+  };
+  auto store_item = [&](int p, int b) {
+    float* w = s_stage + b * F_WROWS * F_WP;
+    if (p == 0) {
+#pragma unroll
+      for (int i = 0; i < NW2; i++) {
+        const int e = t + 256 * i;
+        const int ml = e / g.S, ci = e - ml * g.S;
+        if (e < F_BM * g.S) w[ci * F_WP + ml] = rw[i];
+      }
+      if (s_even != g.S && t < F_BM) w[g.S * F_WP + t] = 0.0f;   // odd S: the chain's last term is 0 x 0
+    } else {
+#pragma unroll
+      for (int i = 0; i < NW2; i++) {
+        const int e = t + 256 * i;
+        const int ml = e / F_WROWS, r = e - ml * F_WROWS;
+        const int ci = r / 9, tap = r - ci * 9;
+        w[(tap * F_CC + ci) * F_WP + ml] = rw[i];
+      }
+    }
+  };
+  // bias + ReLU of wave `wave`'s row to channels choff + m0 .. of `out` (C/D layout as above: 32 consecutive pixels of one
+  // channel per lane group and register)
+  auto write_out = [&](const f32x16 (&val)[2], const float* bias, int m0, int E, int choff) {
+    const int y = y0 + wave, x = x0 + l31;
+    if (y >= g.IH || x >= g.IW) return;
+    float* dst = g.out + ((size_t)img * (g.E1 + g.E3) + choff) * ihw + y * g.IW + x;
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (m < E) {
+          const float v = val[i][r] + bias[m];
+          dst[(size_t)m * ihw] = (v < 0.0f) ? 0.0f : v;
+        }
+      }
+  };
+
+  f32x16 tot[2], comp[2];
+  int j = blockIdx.y, p = 0, b = 0;
+  if (!(j < n1)) advance(j, p);
+  if (j < nsl) load_item(j, p);
+  while (j < nsl) {
+    store_item(p, b);
+    __syncthreads();
+    int jn = j, pn = p;
+    advance(jn, pn);
+    if (jn < nsl) load_item(jn, pn);
+    const float* wb = s_stage + b * F_WROWS * F_WP + lh * F_WP + l31;
+    f32x16 acc[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[i][r] = 0.0f;
+    if (p == 0) {
+      const float* hb = s_sq + lh * V_CH + (wave + 1) * V_PITCH + 1 + l31;
+      for (int k = 0; k < s_even; k += 2) {
+        const float a0 = wb[k * F_WP], a1 = wb[k * F_WP + 32], bv = hb[k * V_CH];
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc[1], 0, 0, 0);
+      }
+      write_out(acc, g.b1, j * F_BM, g.E1, 0);
+    } else {
+      if (p == 1) {
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            tot[i][r] = 0.0f;
+            comp[i][r] = 0.0f;
+          }
+      }
+      const float* hb = s_sq + ((p - 1) * F_CC + lh) * V_CH + wave * V_PITCH + l31;
+      // k-step s = (weight s / 4, channel pair s % 4); the operands of step s + 1 are read before the MFMAs of step s
+      constexpr int STEPS = 9 * F_CC / 2;
+      float a[2][2], bv[2];
+      auto read_step = [&](int s, int q) {
+        const int tap = s / (F_CC / 2), cc = 2 * (s - tap * (F_CC / 2));
+        const int ky = tap / 3, kx = tap - 3 * ky;
+        a[q][0] = wb[(tap * F_CC + cc) * F_WP];
+        a[q][1] = wb[(tap * F_CC + cc) * F_WP + 32];
+        bv[q] = hb[cc * V_CH + ky * V_PITCH + kx];
+      };
+      read_step(0, 0);
+#pragma unroll
+      for (int s = 0; s < STEPS; s++) {
+        if (s + 1 < STEPS) read_step(s + 1, (s + 1) & 1);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s & 1][0], bv[s & 1], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s & 1][1], bv[s & 1], acc[1], 0, 0, 0);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; i++) {  // Kahan, as conv_kernel
+        const f32x16 y = acc[i] - comp[i];
+        const f32x16 s = tot[i] + y;
+        comp[i] = (s - tot[i]) - y;
+        tot[i] = s;
+      }
+      if (p == nc) write_out(tot, g.b3, j * F_BM, g.E3, g.E1);
+    }
+    j = jn, p = pn, b ^= 1;
+  }
+}
+
+// max_pool2d(kernel 3, stride 2, ceil_mode): out[i][y][x] = max over in[i][2y .. min(2y + 2, IH - 1)][2x .. min(2x + 2,
+// IW - 1)], PH = IH / 2, PW = IW / 2 (IH, IW >= 2: torch drops a window that would start outside the input, so an even
+// size ends with a window of two).  A NaN in the part inside the image is the result.
+__global__ void __launch_bounds__(256)
+maxpool3x3s2_ceil_kernel(const float* __restrict__ in, float* __restrict__ out, size_t planes, int IH, int IW, int PH, int PW) {
+  const size_t total = planes * (size_t)PH * (size_t)PW;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t plane = e / ((size_t)PH * PW);
+    const int p = (int)(e - plane * ((size_t)PH * PW));
+    const int y = p / PW, x = p - y * PW;
+    const float* s = in + plane * (size_t)IH * IW + (size_t)(2 * y) * IW + 2 * x;
+    const int nh = (2 * y + 3 <= IH) ? 3 : IH - 2 * y, nw = (2 * x + 3 <= IW) ? 3 : IW - 2 * x;
+    float m = s[0];
+    for (int dy = 0; dy < nh; dy++)
+      for (int dx = 0; dx < nw; dx++) {
+        const float v = s[dy * IW + dx];
+        m = (v > m || v != v) ? v : m;
+      }
+    out[e] = m;
+  }
+}
+
 // sum over the 256 threads of a block in a fixed order (as metrics.hip's); valid in thread 0
 __device__ __forceinline__ double lp_block_sum_256(double v, double* red) {
   red[threadIdx.x] = v;
@@ -473,27 +821,30 @@ layer_distance_kernel(const float* __restrict__ f, int n_pairs, int C, int HW, c
   if (threadIdx.x == 0) partials[(size_t)pair * gridDim.x + blockIdx.x] = tot;
 }
 
+constexpr int LP_MAX_TAPS = 7;
 struct LpipsTaps {
-  size_t first[5];   // where a tap's partials start (in doubles); pair i's blocks at first + i * blocks
-  int blocks[5];
-  double hw[5];
+  size_t first[LP_MAX_TAPS];   // where a tap's partials start (in doubles); pair i's blocks at first + i * blocks
+  int blocks[LP_MAX_TAPS];
+  double hw[LP_MAX_TAPS];
+  int n;                       // taps of the backbone: 5 (alex, vgg) or 7 (squeeze)
 };
 
-// One block per pair: per tap the blocks' sums in index order / HW; out[pair] = (total, layer 1..5)
+// One block per pair: per tap the blocks' sums in index order / HW; out[pair] = (total, layer 1..n)
 __global__ void __launch_bounds__(256) lpips_finish_kernel(const double* __restrict__ partials, LpipsTaps taps, float* __restrict__ out) {
   __shared__ double red[256];
   const int pair = blockIdx.x;
   double total = 0.0;
-  for (int l = 0; l < 5; l++) {
+  const size_t row = (size_t)(taps.n + 1) * pair;
+  for (int l = 0; l < taps.n; l++) {
     const double* src = partials + taps.first[l] + (size_t)pair * taps.blocks[l];
     double s = 0.0;
     for (int i = threadIdx.x; i < taps.blocks[l]; i += 256) s += src[i];
     s = lp_block_sum_256(s, red);
     const double mean = s / taps.hw[l];
     total += mean;
-    if (threadIdx.x == 0) out[6 * (size_t)pair + 1 + l] = (float)mean;
+    if (threadIdx.x == 0) out[row + 1 + l] = (float)mean;
   }
-  if (threadIdx.x == 0) out[6 * (size_t)pair] = (float)total;
+  if (threadIdx.x == 0) out[row] = (float)total;
 }
 
 // ---- host side
@@ -543,6 +894,7 @@ bool lpips_plan(int W, int H, int n_pairs, LpipsPlan& P) {
   }
   // (int32 arithmetic of the kernels: pixels of a call, elements of one image's feature map)
   if (n_img * (size_t)P.oh[0] * P.ow[0] >= ((size_t)1 << 31) || (size_t)3 * H * W >= ((size_t)1 << 31)) return false;
+  P.taps.n = 5;
   P.buf_a = a;
   P.buf_b = b;
   P.off_b = lp_align(a * sizeof(float));
@@ -640,6 +992,7 @@ bool vgg_plan(int W, int H, int n_pairs, VggPlan& P) {
     h /= 2;
     w /= 2;
   }
+  P.taps.n = 5;
   const size_t buf = lp_align(n_img * 64 * (size_t)H * W * sizeof(float));
   P.off_b = buf;
   P.off_partials = 2 * buf;
@@ -647,9 +1000,195 @@ bool vgg_plan(int W, int H, int n_pairs, VggPlan& P) {
   return true;
 }
 
+// ---- SqueezeNet 1.1 (networks.py:69-77): conv 3 x 3 / 2 (no padding), ReLU, pool, Fire 1, Fire 2, pool, Fire 3, Fire 4,
+// pool, Fire 5 .. 8; pools 3 x 3 / 2 in ceil mode; taps: the first ReLU and Fires 2, 4, 5, 6, 7, 8 (each before its pool)
+struct FireShape {
+  int Cin, S, E, tap, pool;   // tap: the tap this module's output is (-1: none); pool: pooled afterwards
+};
+const FireShape SQ_FIRES[8] = {{64, 16, 64, -1, 0},  {128, 16, 64, 1, 1},  {128, 32, 128, -1, 0}, {256, 32, 128, 2, 1},
+                               {256, 48, 192, 3, 0}, {384, 48, 192, 4, 0}, {384, 64, 256, 5, 0},  {512, 64, 256, 6, 0}};
+const int SQ_TAP_C[7] = {64, 128, 256, 384, 384, 512, 512};
+
+size_t fire_tiles(int64_t n_img, int64_t H, int64_t W) { return conv3x3_tiles(n_img, H, W); }
+
+// Grid rows (how many blocks share the expand slabs of one tile; each repeats stage 1): per pixel stage 1 is Cin S
+// multiply-adds (x 1.75 for the halo and the dropped columns) against S (E1 + 9 E3) of stage 2 -- 0.17 to 0.35 of it for
+// the eight SqueezeNet modules -- so one row wherever the tiles alone fill the device, and more only below 256 tiles per
+// image (Fires 5 .. 8 at 1080p have 68).  A function of the layer shape and the image size only.
+int fire_grid_rows(int E1, int E3, int tiles_per_img) {
+  const int n1 = (E1 + F_BM - 1) / F_BM, n3 = (E3 + F_BM - 1) / F_BM, nsl = n1 > n3 ? n1 : n3;
+  const int want = (256 + tiles_per_img - 1) / tiles_per_img;
+  return want < nsl ? want : nsl;
+}
+
+hipError_t launch_fire(FireArgs& g, int n_img, hipStream_t s) {
+  g.tiles_x = (g.IW + V_COLS - 1) / V_COLS;
+  g.tiles_per_img = g.tiles_x * ((g.IH + V_ROWS - 1) / V_ROWS);
+  const dim3 grid((unsigned)((size_t)n_img * g.tiles_per_img), (unsigned)fire_grid_rows(g.E1, g.E3, g.tiles_per_img));
+  if (g.S <= 32)
+    hipLaunchKernelGGL((fire_kernel<1, 16>), grid, dim3(256), 0, s, g);
+  else
+    hipLaunchKernelGGL((fire_kernel<2, 32>), grid, dim3(256), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_maxpool_ceil(const float* in, size_t planes, int IH, int IW, float* out, hipStream_t s) {
+  const int PH = IH / 2, PW = IW / 2;
+  const size_t total = planes * (size_t)PH * PW, want = (total + 255) / 256;
+  hipLaunchKernelGGL(maxpool3x3s2_ceil_kernel, dim3((unsigned)(want < (1u << 20) ? want : (1u << 20))), dim3(256), 0, s, in, out,
+                     planes, IH, IW, PH, PW);
+  return hipGetLastError();
+}
+
+struct SqueezePlan {
+  int h[7], w[7];       // the taps' sizes
+  int fh[8], fw[8];     // the Fire modules' map sizes
+  size_t off_b, off_partials, total_bytes;   // two ping-pong buffers of the first convolution's output, the partials
+  LpipsTaps taps;
+};
+
+// false: an image below 17 x 17, no pairs, or sizes the kernels' 32-bit arithmetic does not cover
+bool squeeze_plan(int W, int H, int n_pairs, SqueezePlan& P) {
+  if (W < Q_MIN || H < Q_MIN || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
+  const size_t n_img = 2 * (size_t)n_pairs;
+  const int h0 = (H - 3) / 2 + 1, w0 = (W - 3) / 2 + 1;
+  // (elements of one input image, of one image's largest feature map, pixels of a call)
+  if ((size_t)3 * H * W >= ((size_t)1 << 31) || (size_t)64 * h0 * w0 >= ((size_t)1 << 31) ||
+      n_img * (size_t)h0 * w0 >= ((size_t)1 << 31))
+    return false;
+  int h = h0, w = w0;
+  P.h[0] = h, P.w[0] = w;
+  h /= 2, w /= 2;
+  for (int f = 0; f < 8; f++) {
+    P.fh[f] = h, P.fw[f] = w;
+    const int t = SQ_FIRES[f].tap;
+    if (t >= 0) P.h[t] = h, P.w[t] = w;
+    if (SQ_FIRES[f].pool) h /= 2, w /= 2;
+  }
+  size_t partial = 0;
+  for (int t = 0; t < 7; t++) {
+    P.taps.first[t] = partial;
+    P.taps.blocks[t] = (P.h[t] * P.w[t] + 255) / 256;
+    P.taps.hw[t] = (double)P.h[t] * (double)P.w[t];
+    partial += (size_t)n_pairs * P.taps.blocks[t];
+  }
+  P.taps.n = 7;
+  const size_t buf = lp_align(n_img * 64 * (size_t)h0 * w0 * sizeof(float));
+  P.off_b = buf;
+  P.off_partials = 2 * buf;
+  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
+  return true;
+}
+
+bool fire_weights_null(const DgsFireWeights& f) {
+  return f.squeeze_w == nullptr || f.squeeze_b == nullptr || f.expand1_w == nullptr || f.expand1_b == nullptr ||
+         f.expand3_w == nullptr || f.expand3_b == nullptr;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dgs_fire_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, int32_t S, int32_t E1, int32_t E3,
+                       const DgsFireWeights* w, float* squeeze_out, float* out, dgs_stream_t stream) {
+  if (in == nullptr || w == nullptr || out == nullptr || fire_weights_null(*w)) return dgs_fail_arg("fire_bias_relu: null pointer");
+  if (n_img < 1 || Cin < 1 || E1 < 1 || E3 < 1 || IH < 1 || IW < 1) return dgs_fail_arg("fire_bias_relu: empty input or output");
+  if (S < 1 || S > F_S_MAX) return dgs_fail_arg("fire_bias_relu: the squeeze depth S is 1..64 (the squeeze map stays in LDS)");
+  if ((int64_t)Cin * IH * IW >= (1ll << 31) || ((int64_t)E1 + E3) * IH * IW >= (1ll << 31) || (int64_t)n_img * IH * IW >= (1ll << 31) ||
+      fire_tiles(n_img, IH, IW) >= ((size_t)1 << 31) || E1 >= (1 << 24) || E3 >= (1 << 24) || Cin >= (1 << 24))
+    return dgs_fail_arg("fire_bias_relu: sizes beyond the kernel's 32-bit index arithmetic");
+  FireArgs g;
+  g.in0 = in, g.in1 = in, g.n_half = n_img;
+  g.sw = w->squeeze_w, g.sb = w->squeeze_b, g.w1 = w->expand1_w, g.b1 = w->expand1_b, g.w3 = w->expand3_w, g.b3 = w->expand3_b;
+  g.sq_out = squeeze_out, g.out = out;
+  g.Cin = Cin, g.IH = IH, g.IW = IW, g.S = S, g.E1 = E1, g.E3 = E3;
+  const hipError_t e = launch_fire(g, n_img, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "fire_bias_relu");
+}
+
+int dgs_maxpool3x3s2_ceil(const float* in, uint64_t planes, int32_t IH, int32_t IW, float* out, dgs_stream_t stream) {
+  if (in == nullptr || out == nullptr) return dgs_fail_arg("maxpool3x3s2_ceil: null pointer");
+  if (planes < 1 || IH < 2 || IW < 2) return dgs_fail_arg("maxpool3x3s2_ceil: no planes, or planes below 2 x 2");
+  if ((int64_t)IH * IW >= (1ll << 31) || planes >= (1ull << 40))
+    return dgs_fail_arg("maxpool3x3s2_ceil: sizes beyond the kernel's index arithmetic");
+  const hipError_t e = launch_maxpool_ceil(in, (size_t)planes, IH, IW, out, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "maxpool3x3s2_ceil");
+}
+
+size_t dgs_lpips_squeeze_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
+  SqueezePlan P;
+  return squeeze_plan(W, H, n_pairs, P) ? P.total_bytes : 0;
+}
+
+int dgs_lpips_squeeze(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsSqueezeWeights* w,
+                      void* tmp, float* out, dgs_stream_t stream) {
+  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr) return dgs_fail_arg("lpips_squeeze: null pointer");
+  if (w->conv_w == nullptr || w->conv_b == nullptr) return dgs_fail_arg("lpips_squeeze: null pointer among the fifty-seven weight pointers");
+  for (int f = 0; f < 8; f++)
+    if (fire_weights_null(w->fire[f])) return dgs_fail_arg("lpips_squeeze: null pointer among the fifty-seven weight pointers");
+  for (int t = 0; t < 7; t++)
+    if (w->lin[t] == nullptr) return dgs_fail_arg("lpips_squeeze: null pointer among the fifty-seven weight pointers");
+  if (n_pairs < 1) return dgs_fail_arg("lpips_squeeze: n_pairs must be at least 1");
+  if (W < Q_MIN || H < Q_MIN) return dgs_fail_arg("lpips_squeeze: the smallest image the network accepts is 17 x 17 (W and H >= 17)");
+  SqueezePlan P;
+  if (!squeeze_plan(W, H, n_pairs, P)) return dgs_fail_arg("lpips_squeeze: more than 65535 pairs or more pixels than one call covers");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(tmp);
+  float* bufs[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + P.off_b)};
+  double* partials = reinterpret_cast<double*>(base + P.off_partials);
+  const int n_img = 2 * n_pairs;
+  int which = 0;                // the buffer the next kernel writes
+  auto distance = [&](const float* f, int t) {
+    hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[t], (unsigned)n_pairs), dim3(256), 0, s, f, (int)n_pairs,
+                       SQ_TAP_C[t], P.h[t] * P.w[t], w->lin[t], partials + P.taps.first[t]);
+    return hipGetLastError();
+  };
+
+  // the first convolution on the generic kernel: 3 x 3, stride 2, no padding, the z-score fused into its gather
+  ConvArgs c;
+  c.in0 = a, c.in1 = b, c.n_half = n_pairs;
+  c.w = w->conv_w, c.bias = w->conv_b;
+  c.out = bufs[which];
+  c.Cin = 3, c.IH = H, c.IW = W, c.Cout = 64, c.OH = P.h[0], c.OW = P.w[0];
+  c.KH = 3, c.KW = 3, c.stride = 2, c.pad = 0, c.K = 27, c.N = n_img * P.h[0] * P.w[0];
+  hipError_t e = launch_conv(c, true, s);
+  if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (convolution)");
+  const float* cur = bufs[which];
+  which ^= 1;
+  e = distance(cur, 0);
+  if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (layer distance)");
+  e = launch_maxpool_ceil(cur, (size_t)n_img * 64, P.h[0], P.w[0], bufs[which], s);
+  if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (max-pool)");
+  cur = bufs[which];
+  which ^= 1;
+
+  for (int f = 0; f < 8; f++) {
+    const FireShape& F = SQ_FIRES[f];
+    const DgsFireWeights& fw = w->fire[f];
+    FireArgs g;
+    g.in0 = cur, g.in1 = cur, g.n_half = n_img;
+    g.sw = fw.squeeze_w, g.sb = fw.squeeze_b, g.w1 = fw.expand1_w, g.b1 = fw.expand1_b, g.w3 = fw.expand3_w, g.b3 = fw.expand3_b;
+    g.sq_out = nullptr, g.out = bufs[which];
+    g.Cin = F.Cin, g.IH = P.fh[f], g.IW = P.fw[f], g.S = F.S, g.E1 = F.E, g.E3 = F.E;
+    e = launch_fire(g, n_img, s);
+    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (Fire module)");
+    cur = bufs[which];
+    which ^= 1;
+    if (F.tap >= 0) {
+      e = distance(cur, F.tap);
+      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (layer distance)");
+    }
+    if (F.pool) {
+      e = launch_maxpool_ceil(cur, (size_t)n_img * 2 * F.E, P.fh[f], P.fw[f], bufs[which], s);
+      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (max-pool)");
+      cur = bufs[which];
+      which ^= 1;
+    }
+  }
+  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
+  e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_squeeze (finish)");
+}
 
 int dgs_conv2d_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
                          const float* bias, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t zscore,

@@ -44,7 +44,7 @@ One difference from the sequential fit: there a forward that overflows its capac
 epoch of its group's rows (all n steps of those rows, zero-gradient ones included) -- dropped() counts the view-steps.
 
 LPIPS, the third number, needs network weights that are not part of this package: `evaluate(..., lpips=weights)` with a
-caller's lpips.LPIPSWeights returns (psnr, ssim, lpips) (dgs_lpips_alex on the device); without it, (psnr, ssim).
+caller's lpips.LPIPSWeights (or LPIPSVggWeights, LPIPSSqueezeWeights) returns (psnr, ssim, lpips) (dgs_lpips_alex / _vgg / _squeeze on the device); without it, (psnr, ssim).
 `initialize_test_pose` (COLMAP registration of unposed test images) and the dataset readers are out of scope.
 """
 import ctypes

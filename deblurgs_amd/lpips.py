@@ -27,6 +27,15 @@ after convolutions 2, 4, 7 and 10; taps after convolutions 2, 4, 7, 10 (before t
 VGG16 state dict and the published `vgg.pth`; fp32 device inputs run dgs_lpips_vgg (csrc/lpips.hip: conv3x3_kernel reads
 its operands from an input halo tile in LDS).  Which backbone a call runs is the weights' `net_type`.
 tests/golden/lpips_vgg_golden.npz pins both paths.
+
+SqueezeNet 1.1 (`net_type='squeeze'`, networks.py:69-77): the same z-score, conv 3->64 3x3 /2 without padding, ReLU,
+max-pool, Fire 1, Fire 2, max-pool, Fire 3, Fire 4, max-pool, Fire 5 .. 8 -- a Fire module is
+cat(relu(expand1x1(s)), relu(expand3x3(s, pad 1))) with s = relu(squeeze(x)), the max-pools are 3x3 /2 with
+ceil_mode=True; seven taps: the first ReLU and Fires 2, 4, 5, 6, 7, 8, each before the pool that follows it
+(`features` modules 2, 5, 8, 10, 11, 12, 13 counted from 1); the smallest image is 17 x 17 and the result has eight
+columns.  `LPIPSSqueezeWeights` takes torchvision's squeezenet1_1 state dict and the published `squeeze.pth`; fp32 device
+inputs run dgs_lpips_squeeze (csrc/lpips.hip: fire_kernel makes a whole Fire module in one launch, the squeeze map never
+leaves LDS).  tests/golden/lpips_squeeze_golden.npz pins both paths.
 """
 import ctypes
 import glob
@@ -52,6 +61,16 @@ VGG_FEATURE_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
 VGG_TAP = (None, 0, None, 1, None, None, 2, None, None, 3, None, None, 4)
 VGG_CHANNELS = (64, 128, 256, 512, 512)
 VGG_MIN_SIZE = 16
+# SqueezeNet 1.1: (Cin, S, E) of the eight Fire modules, their index in torchvision's `features`, the tap each one feeds
+# (or None), whether a ceil-mode pool follows
+SQUEEZE_FIRES = ((64, 16, 64), (128, 16, 64), (128, 32, 128), (256, 32, 128), (256, 48, 192), (384, 48, 192), (384, 64, 256),
+                 (512, 64, 256))
+SQUEEZE_FEATURE_INDEX = (3, 4, 6, 7, 9, 10, 11, 12)
+SQUEEZE_TAP = (None, 1, None, 2, 3, 4, 5, 6)
+SQUEEZE_POOL = (False, True, False, True, False, False, False, False)
+SQUEEZE_CHANNELS = (64, 128, 256, 384, 384, 512, 512)
+SQUEEZE_MIN_SIZE = 17
+FIRE_PARTS = ("squeeze", "expand1x1", "expand3x3")
 MAX_TMP_BYTES = 4 << 30
 
 
@@ -173,6 +192,77 @@ class LPIPSVggWeights:
         return self._struct
 
 
+class LPIPSSqueezeWeights:
+    """The fifty-seven tensors of LPIPS-squeeze: `conv_w` [64,3,3,3], `conv_b` [64]; `fire[i]` = (squeeze_w [S,Cin,1,1],
+    squeeze_b [S], expand1_w [E,S,1,1], expand1_b [E], expand3_w [E,S,3,3], expand3_b [E]) for the eight Fire modules;
+    `lin[i]` [1,C,1,1] (7)."""
+    net_type = "squeeze"
+    min_size = SQUEEZE_MIN_SIZE
+
+    def __init__(self, conv_w, conv_b, fire, lin):
+        self.conv_w, self.conv_b, self.fire, self.lin = conv_w, conv_b, [tuple(f) for f in fire], list(lin)
+        self._struct = None
+
+    @classmethod
+    def from_state_dicts(cls, features_sd, lin_sd):
+        """features_sd: torchvision's squeezenet1_1 state dict (`features.0.{weight,bias}`,
+        `features.{3,4,6,7,9,10,11,12}.{squeeze,expand1x1,expand3x3}.{weight,bias}`) or that of its `.features` alone;
+        lin_sd: the published `lin{i}.model.1.weight` of squeeze.pth, or the reference's renamed `{i}.1.weight`.  A missing
+        key or a wrong shape raises with the key named."""
+        def get(key, shape):
+            name, t = _pick(features_sd, (f"features.{key}", key), f"features.{key}")
+            return _as_f32(name, t, shape)
+        conv_w, conv_b = get("0.weight", (64, 3, 3, 3)), get("0.bias", (64,))
+        fire, lin = [], []
+        for idx, (ci, sq, e) in zip(SQUEEZE_FEATURE_INDEX, SQUEEZE_FIRES):
+            shapes = ((sq, ci, 1, 1), (e, sq, 1, 1), (e, sq, 3, 3))
+            six = []
+            for part, shape in zip(FIRE_PARTS, shapes):
+                six += [get(f"{idx}.{part}.weight", shape), get(f"{idx}.{part}.bias", (shape[0],))]
+            fire.append(tuple(six))
+        for i, c in enumerate(SQUEEZE_CHANNELS):
+            name, t = _pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight")
+            lin.append(_as_f32(name, t, (1, c, 1, 1)))
+        return cls(conv_w, conv_b, fire, lin)
+
+    @classmethod
+    def load(cls, backbone_path, lin_path):
+        """The two local checkpoint files (torch.load on the CPU, tensors only)."""
+        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu", weights_only=True),
+                                    torch.load(lin_path, map_location="cpu", weights_only=True))
+
+    def tensors(self):
+        return [self.conv_w, self.conv_b] + [t for f in self.fire for t in f] + self.lin
+
+    @property
+    def device(self):
+        return self.conv_w.device
+
+    def to(self, device):
+        return LPIPSSqueezeWeights(self.conv_w.to(device), self.conv_b.to(device),
+                                   [tuple(t.to(device) for t in f) for f in self.fire], [t.to(device) for t in self.lin])
+
+    def struct(self):
+        """The DgsLpipsSqueezeWeights of these tensors (they stay alive with this object)."""
+        if self._struct is None:
+            s = _lib.DgsLpipsSqueezeWeights()
+            s.conv_w, s.conv_b = self.conv_w.data_ptr(), self.conv_b.data_ptr()
+            for i, six in enumerate(self.fire):
+                for (field, _), t in zip(_lib.DgsFireWeights._fields_, six):
+                    setattr(s.fire[i], field, t.data_ptr())
+            for i in range(7):
+                s.lin[i] = self.lin[i].data_ptr()
+            self._struct = s
+        return self._struct
+
+
+def _fire_torch(x, six):
+    """A Fire module (torchvision's squeezenet.py): six = (squeeze_w, squeeze_b, expand1_w, expand1_b, expand3_w, expand3_b)
+    in x's dtype on x's device."""
+    s = F.relu(F.conv2d(x, six[0], six[1]))
+    return torch.cat([F.relu(F.conv2d(s, six[2], six[3])), F.relu(F.conv2d(s, six[4], six[5], padding=1))], dim=1)
+
+
 def _batched(x, y, min_size=MIN_SIZE):
     if x.shape != y.shape or x.dim() not in (3, 4) or x.shape[-3] != 3:
         raise ValueError(f"lpips takes two [3,H,W] or [N,3,H,W] tensors of one shape (got {tuple(x.shape)}, {tuple(y.shape)})")
@@ -183,10 +273,22 @@ def _batched(x, y, min_size=MIN_SIZE):
     return x, y
 
 def _features_torch(x, w):
-    """The five normalised taps of x [N,3,H,W] (networks.py:53-66) in x's dtype on x's device."""
+    """The normalised taps of x [N,3,H,W] (networks.py:53-66; five, for squeeze seven) in x's dtype on x's device."""
     t = lambda a: a.to(device=x.device, dtype=x.dtype)
     x = (x - t(torch.tensor(MEAN))[None, :, None, None]) / t(torch.tensor(STD))[None, :, None, None]
     out = []
+    norm = lambda a: a / (torch.sqrt(torch.sum(a ** 2, dim=1, keepdim=True)) + 1e-10)
+    if w.net_type == "squeeze":                             # networks.py:69-77
+        x = F.relu(F.conv2d(x, t(w.conv_w), t(w.conv_b), stride=2))
+        out.append(norm(x))
+        x = F.max_pool2d(x, kernel_size=3, stride=2, ceil_mode=True)
+        for six, tap, pool in zip(w.fire, SQUEEZE_TAP, SQUEEZE_POOL):
+            x = _fire_torch(x, [t(a) for a in six])
+            if tap is not None:
+                out.append(norm(x))
+            if pool:
+                x = F.max_pool2d(x, kernel_size=3, stride=2, ceil_mode=True)
+        return out
     if w.net_type == "vgg":                                 # networks.py:88-96
         for i, tap in enumerate(VGG_TAP):
             x = F.relu(F.conv2d(x, t(w.conv_w[i]), t(w.conv_b[i]), stride=1, padding=1))
@@ -206,8 +308,8 @@ def _features_torch(x, w):
 def _layers_torch(x, y, w):
     fx, fy = _features_torch(x, w), _features_torch(y, w)
     res = [F.conv2d((a - b) ** 2, w.lin[i].to(device=x.device, dtype=x.dtype)).mean((2, 3)) for i, (a, b) in enumerate(zip(fx, fy))]
-    layers = torch.cat(res, dim=1)                                           # [N,5]
-    return torch.cat([layers.sum(dim=1, keepdim=True), layers], dim=1)       # [N,6]
+    layers = torch.cat(res, dim=1)                                           # [N,5] (squeeze: [N,7])
+    return torch.cat([layers.sum(dim=1, keepdim=True), layers], dim=1)       # [N,6] (squeeze: [N,8])
 
 
 def _fused_ok(x, y):
@@ -216,10 +318,11 @@ def _fused_ok(x, y):
 
 def lpips_layers(x, y, weights, max_tmp_bytes=MAX_TMP_BYTES):
     """[N,6] = (total, layer 1..5) per pair of x, y ([3,H,W] or [N,3,H,W]) with the backbone of `weights` (LPIPSWeights:
-    alex, LPIPSVggWeights: vgg).  fp32 device inputs: dgs_lpips_alex / dgs_lpips_vgg on the current stream (the weights
-    must live on that device), no host synchronisation; otherwise the torch expressions in the inputs' dtype.  A vgg batch
-    whose scratch would pass max_tmp_bytes is cut into consecutive calls: a pair's numbers do not depend on the other
-    pairs of its call, so the result is the same bit for bit."""
+    alex, LPIPSVggWeights: vgg, LPIPSSqueezeWeights: squeeze, whose seven taps give [N,8]).  fp32 device inputs:
+    dgs_lpips_alex / dgs_lpips_vgg / dgs_lpips_squeeze on the current stream (the weights must live on that device), no
+    host synchronisation; otherwise the torch expressions in the inputs' dtype.  A vgg or squeeze batch whose scratch
+    would pass max_tmp_bytes is cut into consecutive calls: a pair's numbers do not depend on the other pairs of its
+    call, so the result is the same bit for bit."""
     x, y = _batched(x, y, weights.min_size)
     if not _fused_ok(x, y):
         return _layers_torch(x, y, weights)
@@ -228,17 +331,19 @@ def lpips_layers(x, y, weights, max_tmp_bytes=MAX_TMP_BYTES):
     x, y = x.contiguous(), y.contiguous()
     L = _lib.lib()
     N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    out = torch.empty((N, 6), dtype=torch.float32, device=x.device)
+    out = torch.empty((N, 8 if weights.net_type == "squeeze" else 6), dtype=torch.float32, device=x.device)
     st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    if weights.net_type == "vgg":
+    if weights.net_type in ("vgg", "squeeze"):
+        name = "dgs_lpips_" + weights.net_type
+        call, tmp_bytes = getattr(L, name), getattr(L, name + "_tmp_bytes")
         per_call = N
-        while per_call > 1 and L.dgs_lpips_vgg_tmp_bytes(W, H, per_call) > max_tmp_bytes:
+        while per_call > 1 and tmp_bytes(W, H, per_call) > max_tmp_bytes:
             per_call = (per_call + 1) // 2
-        tmp = torch.empty(L.dgs_lpips_vgg_tmp_bytes(W, H, per_call), dtype=torch.uint8, device=x.device)
+        tmp = torch.empty(tmp_bytes(W, H, per_call), dtype=torch.uint8, device=x.device)
         for i in range(0, N, per_call):
             n = min(per_call, N - i)
-            _lib.check(L.dgs_lpips_vgg(x[i:i + n].data_ptr(), y[i:i + n].data_ptr(), n, W, H, ctypes.byref(weights.struct()),
-                                       tmp.data_ptr(), out[i:i + n].data_ptr(), st), "dgs_lpips_vgg")
+            _lib.check(call(x[i:i + n].data_ptr(), y[i:i + n].data_ptr(), n, W, H, ctypes.byref(weights.struct()),
+                            tmp.data_ptr(), out[i:i + n].data_ptr(), st), name)
         return out
     tmp = torch.empty(L.dgs_lpips_alex_tmp_bytes(W, H, N), dtype=torch.uint8, device=x.device)
     _lib.check(L.dgs_lpips_alex(x.data_ptr(), y.data_ptr(), N, W, H, ctypes.byref(weights.struct()), tmp.data_ptr(),
@@ -295,16 +400,58 @@ def maxpool2x2(x):
     return out
 
 
+def fire_bias_relu(x, weights6, return_squeeze=False):
+    """A Fire module, cat(relu(conv1x1(s)), relu(conv3x3(s, pad 1))) with s = relu(conv1x1(x)), through dgs_fire_bias_relu,
+    the one-launch kernel of dgs_lpips_squeeze on its own.  weights6 = (squeeze_w [S,Cin,1,1], squeeze_b [S], expand1_w
+    [E1,S,1,1], expand1_b [E1], expand3_w [E3,S,3,3], expand3_b [E3]), S <= 64.  return_squeeze: also the squeeze map the
+    kernel computed, (out, s).  No fallback."""
+    ws = tuple(weights6)
+    if len(ws) != 6 or not all(_fused_ok(x, w) for w in ws) or x.dim() != 4:
+        raise RuntimeError("fire_bias_relu needs float32 tensors on one HIP device: x [N,Cin,H,W] and the six Fire weights")
+    x = x.contiguous()
+    ws = tuple(w.contiguous() for w in ws)
+    N, Cin, IH, IW = (int(v) for v in x.shape)
+    S, E1, E3 = int(ws[0].shape[0]), int(ws[2].shape[0]), int(ws[4].shape[0])
+    want = ((S, Cin, 1, 1), (S,), (E1, S, 1, 1), (E1,), (E3, S, 3, 3), (E3,))
+    if [tuple(w.shape) for w in ws] != list(want):
+        raise ValueError("fire_bias_relu: the weights are squeeze [S,Cin,1,1], [S], expand1x1 [E1,S,1,1], [E1], expand3x3 "
+                         "[E3,S,3,3], [E3]")
+    out = torch.empty((N, E1 + E3, IH, IW), dtype=torch.float32, device=x.device)
+    sq = torch.empty((N, S, IH, IW), dtype=torch.float32, device=x.device) if return_squeeze else None
+    fw = _lib.DgsFireWeights(*[w.data_ptr() for w in ws])
+    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.lib().dgs_fire_bias_relu(x.data_ptr(), N, Cin, IH, IW, S, E1, E3, ctypes.byref(fw),
+                                             sq.data_ptr() if return_squeeze else None, out.data_ptr(), st),
+               "dgs_fire_bias_relu")
+    return (out, sq) if return_squeeze else out
+
+
+def maxpool3x3s2_ceil(x):
+    """max_pool2d(x, 3, 2, ceil_mode=True) of a float32 device tensor [..., H, W] through dgs_maxpool3x3s2_ceil.  No
+    fallback."""
+    if not _fused_ok(x, x) or x.dim() < 2:
+        raise RuntimeError("maxpool3x3s2_ceil needs a float32 tensor [..., H, W] on a HIP device")
+    x = x.contiguous()
+    IH, IW = int(x.shape[-2]), int(x.shape[-1])
+    planes = x.numel() // max(IH * IW, 1)
+    out = torch.empty(tuple(x.shape[:-2]) + (IH // 2, IW // 2), dtype=torch.float32, device=x.device)
+    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.lib().dgs_maxpool3x3s2_ceil(x.data_ptr(), planes, IH, IW, out.data_ptr(), st), "dgs_maxpool3x3s2_ceil")
+    return out
+
+
 def lpips(x, y, weights):
     """The reference's criterion (lpips.py:28-36): [3,H,W] or [N,3,H,W] in, ONE [1,1,1,1] tensor out -- the sum over the
-    five layers and over the batch."""
+    layers and over the batch."""
     return lpips_layers(x, y, weights)[:, 0].sum().reshape(1, 1, 1, 1)
 
 
 # ---- the weights the drop-in `lpipsPyTorch.lpips` uses
-_default = {"alex": {}, "vgg": {}}
+_default = {"alex": {}, "vgg": {}, "squeeze": {}}
 # per backbone: the class, torchvision's checkpoint (a glob), the LPIPS v0.1 linear layers
-_FILES = {"alex": (LPIPSWeights, "alexnet-owt-*.pth", "alex.pth"), "vgg": (LPIPSVggWeights, "vgg16-*.pth", "vgg.pth")}
+_FILES = {"alex": (LPIPSWeights, "alexnet-owt-*.pth", "alex.pth"), "vgg": (LPIPSVggWeights, "vgg16-*.pth", "vgg.pth"),
+          "squeeze": (LPIPSSqueezeWeights, "squeezenet1_1-*.pth", "squeeze.pth")}
+_BACKBONE_NAME = {"alex": "AlexNet", "vgg": "VGG16", "squeeze": "SqueezeNet 1.1"}
 
 
 def set_default_weights(weights):
@@ -337,7 +484,7 @@ def default_weights(device, net_type="alex"):
         if not backbone or not os.path.exists(lin):
             raise FileNotFoundError(
                 f"LPIPS needs two weight files and neither ships with this package: torchvision's "
-                f"{'AlexNet' if net_type == 'alex' else 'VGG16'} checkpoint ({backbone_glob}) and the LPIPS v0.1 linear layers "
+                f"{_BACKBONE_NAME[net_type]} checkpoint ({backbone_glob}) and the LPIPS v0.1 linear layers "
                 f"({lin_name}).  Put both into {ckpt}, or call "
                 f"deblurgs_amd.lpips.set_default_weights({cls.__name__}.load(backbone_path, lin_path)).")
         w = cls.load(backbone[-1], lin).to(device)

@@ -732,6 +732,66 @@ int dgs_conv3x3_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t I
  * a window is its result.  `out` must not overlap `in`. */
 int dgs_maxpool2x2(const float* in, uint64_t planes, int32_t IH, int32_t IW, float* out, dgs_stream_t stream);
 
+/* ---- LPIPS with the SqueezeNet 1.1 backbone (additions to ABI 15; networks.py:69-77 of the reference) ----
+ * lpips(x, y, net_type='squeeze'), again with CALLER-SUPPLIED weights.  torchvision's squeezenet1_1().features shapes:
+ *   conv_w, conv_b   [64,3,3,3], [64]                                                        (features.0)
+ *   fire[0..7]       the Fire modules features.3/4/6/7/9/10/11/12, (Cin, S, E) = (64,16,64) (128,16,64) (128,32,128)
+ *                    (256,32,128) (256,48,192) (384,48,192) (384,64,256) (512,64,256): squeeze_w [S,Cin,1,1], squeeze_b [S],
+ *                    expand1_w [E,S,1,1], expand1_b [E], expand3_w [E,S,3,3], expand3_b [E]
+ *   lin[0..6]        [1,C,1,1], C = 64, 128, 256, 384, 384, 512, 512   (LPIPS v0.1 lin{i}.model.1.weight of squeeze.pth)
+ * all fp32, contiguous, in device memory. */
+typedef struct DgsFireWeights {
+  const float* squeeze_w;
+  const float* squeeze_b;
+  const float* expand1_w;
+  const float* expand1_b;
+  const float* expand3_w;
+  const float* expand3_b;
+} DgsFireWeights;
+typedef struct DgsLpipsSqueezeWeights {
+  const float* conv_w;
+  const float* conv_b;
+  DgsFireWeights fire[8];
+  const float* lin[7];
+} DgsLpipsSqueezeWeights;
+/* As dgs_lpips_alex, with the network z-score, then conv 3x3 /2 without padding, ReLU, max-pool, Fire 1, Fire 2, max-pool,
+ * Fire 3, Fire 4, max-pool, Fire 5 .. 8; the max-pools are 3x3 /2 in ceil mode; taps: the first ReLU and the outputs of
+ * Fires 2, 4, 5, 6, 7, 8 (each before the pool that follows it) -- `features` modules 2, 5, 8, 10, 11, 12, 13 counted from
+ * 1.  out [n_pairs,8] = per pair (total, layer 1..7).  The first convolution runs on dgs_conv2d_bias_relu's kernel, every
+ * Fire module in one launch of dgs_fire_bias_relu's.  Every contract of dgs_lpips_vgg holds: stream-explicit, caller-owned
+ * memory, no host synchronisation, no float atomics, a pair's eight numbers independent of the other pairs and of
+ * n_pairs, two runs bitwise equal, lpips(x, x) exactly 0 in all eight and lpips(x, y) == lpips(y, x) bitwise.
+ * tmp >= dgs_lpips_squeeze_tmp_bytes(W, H, n_pairs) bytes (0: arguments the call refuses), 256-byte aligned: two ping-pong
+ * buffers of the first convolution's output [2 n_pairs,64,(H-3)/2+1,(W-3)/2+1] and the distance partials -- 529,328,896
+ * bytes for one 1920 x 1080 pair.  Refused before any HIP call: a NULL pointer (the fifty-seven of `w` included),
+ * n_pairs < 1 (or above 65535), W or H below 17 -- the smallest image the network accepts, as the reference raises at
+ * 16 -- and 3 H W, 64 h0 w0 or 2 n_pairs h0 w0 of 2^31 and more (h0 = (H-3)/2+1, w0 = (W-3)/2+1). */
+size_t dgs_lpips_squeeze_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs);
+int dgs_lpips_squeeze(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsSqueezeWeights* w,
+                      void* tmp, float* out, dgs_stream_t stream);
+/* A Fire module on its own, in one launch: out [n_img,E1+E3,IH,IW] = cat(relu(conv1x1(s, expand1)), relu(conv3x3(s,
+ * expand3, zero padding 1))) with s = relu(conv1x1(in [n_img,Cin,IH,IW], squeeze)) [n_img,S,IH,IW], on
+ * v_mfma_f32_32x32x2_f32.  s is computed per output tile (4 rows x 32 columns, with its 1-pixel halo) and kept in LDS;
+ * both expands write straight into their channel ranges of `out`.  Any Cin >= 1, 1 <= S <= 64 (a larger S is refused),
+ * E1, E3 >= 1.  squeeze_out non-NULL: s is also stored there (each element once); `out` is bit-identical either way.
+ * Every element, fp32 throughout, whatever its place in the call or in a tile:
+ *   s:           per chunk of CK input channels (CK = 16 where S <= 32, else 32) one fmaf chain of L1 = CK terms from 0 in
+ *                channel order (a term past Cin being 0 x 0), the chunks' results added in channel order with a
+ *                compensated (Kahan) fp32 sum, + bias, ReLU (a NaN passes);
+ *   1 x 1 part:  ONE fmaf chain of L2a = S terms from 0 in channel order (S + 1 for odd S: a last 0 x 0), + bias, ReLU;
+ *   3 x 3 part:  per chunk of 8 squeeze channels one fmaf chain of L2b = 72 terms from 0 in the k order (ky, kx, ci) -- for
+ *                each of the nine weights in row-major order the chunk's channels in order, a term past S being 0 x 0 --,
+ *                the chunks' results added in channel order with the compensated sum, + bias, ReLU; the zero padding
+ *                pads s (a position outside the image is 0, not relu(bias)).
+ * Refused before any HIP call: a NULL pointer (squeeze_out excepted; the six of `w` included), an empty size, S above 64,
+ * and Cin IH IW, (E1 + E3) IH IW or n_img IH IW of 2^31 and more.  `out` and squeeze_out must not overlap `in`. */
+int dgs_fire_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, int32_t S, int32_t E1, int32_t E3,
+                       const DgsFireWeights* w, float* squeeze_out, float* out, dgs_stream_t stream);
+/* max_pool2d(kernel 3, stride 2, ceil_mode=True) of `planes` planes [IH,IW] -> [IH / 2, IW / 2] (IH, IW >= 2: a window
+ * that would start outside the input is dropped, so an even size ends with a window of two rows or columns); the maximum
+ * over the part of a window inside the plane, a NaN in that part is its result.  `out` must not overlap `in`. */
+int dgs_maxpool3x3s2_ceil(const float* in, uint64_t planes, int32_t IH, int32_t IW, float* out, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
