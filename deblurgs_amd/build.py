@@ -38,6 +38,8 @@ SOURCES = {
     # LPIPS: the convolution's compensated (Kahan) sum must not be contracted across its statements; the z-score and the
     # layer distance round once per statement, as the torch expressions do (the MFMA chains are builtins: unaffected)
     "lpips.hip": ["-ffp-contract=off"],
+    # the tile-list profile: integers only
+    "listprof.hip": [],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -792,6 +792,32 @@ int dgs_fire_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, 
  * over the part of a window inside the plane, a NaN in that part is its result.  `out` must not overlap `in`. */
 int dgs_maxpool3x3s2_ceil(const float* in, uint64_t planes, int32_t IH, int32_t IW, float* out, dgs_stream_t stream);
 
+/* ---- tile-list profile (addition to ABI 15; no counterpart in the reference) ----
+ * How long are the tile lists of a forward, how far did the forward walk them, and how uneven is that work: the figures
+ * behind any decision about splitting long lists or balancing tiles.  Reads what a forward left in the image blob:
+ *   ranges     u32 [K*T,2], the blob's `ranges` (DgsLayout.ranges; offset 0 of a forward_only blob), T = ceil(W/16) ceil(H/16)
+ *   n_contrib  u32 [K,H*W], the blob's `n_contrib`, or NULL (a forward_only blob has none): the walked figures are then 0
+ * Per (subframe, tile), into per_tile u32 [K*T,2] when it is not NULL:
+ *   length = ranges.y - ranges.x
+ *   walked = the largest n_contrib among the tile's pixels INSIDE the image: the list position after which the forward had
+ *            nothing left to do for the tile (its wave stops there), so the work the tile really cost
+ * summary u64 [K+1, DGS_LIST_PROFILE_WORDS]: row k < K is subframe k, row K all subframes together.  Words of a row:
+ *   0 tiles          1 nonempty (length > 0)   2 total = sum of length   3 max_length
+ *   4 batches = sum of ceil(length / 64), the compositing kernels' unit of work
+ *   5 walked_total   6 walked_max              7 walked_batches = sum of ceil(walked / 64)
+ *   8..40  hist_length[33]:  bucket 0 counts the tiles with length 0, bucket b >= 1 those with length in [2^(b-1), 2^b)
+ *   41..73 hist_walked[33]:  the same of walked
+ * One wave64 per tile with the compositing kernels' pixel mapping (four loads per lane, a cross-lane max); a block adds
+ * its 32 tiles in LDS with integer atomics and stores one partial row into tmp, a second launch adds the partial rows.
+ * Integers only, no global and no float atomics: the result is bitwise reproducible.  Two launches on `stream`, no host
+ * synchronisation, no allocation, nothing kept between calls: capturable.  tmp >= dgs_list_profile_tmp_bytes(W, H, K)
+ * bytes (0 for sizes the call refuses); ranges, per_tile, summary and tmp 8-byte aligned.  Refused before anything is
+ * enqueued: a NULL ranges / summary / tmp, W or H outside 1..65536, K outside 1..DGS_MAX_K, a misaligned pointer. */
+#define DGS_LIST_PROFILE_WORDS 74
+size_t dgs_list_profile_tmp_bytes(int32_t W, int32_t H, int32_t K);
+int dgs_list_profile(const uint32_t* ranges, const uint32_t* n_contrib, int32_t W, int32_t H, int32_t K, uint32_t* per_tile,
+                     uint64_t* summary, void* tmp, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
