@@ -253,6 +253,10 @@ EXPORTS = {
                               [ctypes.c_void_p] * 2),
     "dgs_list_profile_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
     "dgs_list_profile": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4),
+    "dgs_box_reduce_u8": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2),
+    "dgs_sad_matrix_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64]),
+    "dgs_sad_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.c_uint64] + [ctypes.c_void_p] * 3),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

@@ -40,6 +40,8 @@ SOURCES = {
     "lpips.hip": ["-ffp-contract=off"],
     # the tile-list profile: integers only
     "listprof.hip": [],
+    # box means and SAD matrices of 8-bit frames: integers only
+    "register.hip": [],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -45,7 +45,9 @@ epoch of its group's rows (all n steps of those rows, zero-gradient ones include
 
 LPIPS, the third number, needs network weights that are not part of this package: `evaluate(..., lpips=weights)` with a
 caller's lpips.LPIPSWeights (or LPIPSVggWeights, LPIPSSqueezeWeights) returns (psnr, ssim, lpips) (dgs_lpips_alex / _vgg / _squeeze on the device); without it, (psnr, ssim).
-`initialize_test_pose` (COLMAP registration of unposed test images) and the dataset readers are out of scope.
+`initialize_test_pose` (test.py:188-398) gives unposed test images their starting poses.  The reference registers them with a
+COLMAP binary; here it is coarse photometric registration against the trained cloud (registration.py) -- a different method.
+The dataset readers are out of scope.
 """
 import ctypes
 import math
@@ -578,6 +580,15 @@ def optimize_test_pose(cloud, cams, gt_images, bg, tone_mapping, num_iter_per_vi
         raise RuntimeError(f"{drops} of {fit.steps} pose-fit steps exceeded the duplicate capacity ({fit.capacity}) and "
                            f"were skipped; fit again with {type(fit).__name__}(capacity=...) sized for the poses it moves through")
     return fit.cameras()
+
+
+def initialize_test_pose(motion, cloud, test_images, bg, tone_mapping=None, **kw):
+    """Starting poses for unposed test images, the place of test.py:188-398: [TestCamera] * n (original_image set) for
+    optimize_test_pose.  This is coarse photometric registration and NOT the reference's COLMAP registration: renders of
+    poses along the learned training trajectories are scored against every test image on the device and the best one is
+    polished by a short pattern search (registration.seed_test_poses, which takes **kw and returns the scores too)."""
+    from . import registration
+    return registration.seed_test_poses(motion, cloud, test_images, bg, tone_mapping, **kw).cameras
 
 
 def _write_view(vis_dir, i, image, gt, writer):

@@ -818,6 +818,33 @@ size_t dgs_list_profile_tmp_bytes(int32_t W, int32_t H, int32_t K);
 int dgs_list_profile(const uint32_t* ranges, const uint32_t* n_contrib, int32_t W, int32_t H, int32_t K, uint32_t* per_tile,
                      uint64_t* summary, void* tmp, dgs_stream_t stream);
 
+/* ---- photometric registration (additions to ABI 15; the reference shells out to COLMAP for this step, test.py:188-398) ----
+ * Two integer kernels on the 8-bit frames dgs_frames_finish makes; every result is exact and bitwise reproducible.  No
+ * atomics, no host synchronisation, no allocation, nothing kept between calls: capturable.
+ *
+ * dgs_box_reduce_u8: in u8 [G,H,W,3] (any alignment) -> out u32 [G,pitch], h = H / s, w = W / s (floor: trailing rows and
+ * columns are dropped), pitch = (h w + 3) & ~3 dwords.  Output pixel (y, x) of image g is dword y w + x of row g:
+ * r | g << 8 | b << 16, top byte 0, each channel (sum of its s s bytes + s s / 2) / (s s) in integer arithmetic; the pad
+ * dwords of a row are written as 0.  s = 1 packs.  Refused before anything is enqueued: a NULL pointer, G outside 1..65535,
+ * s outside 1..64, H / s or W / s below 1, more than 2^30 output pixels per image, an `out` that is not 16-byte aligned. */
+int dgs_box_reduce_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t s, uint32_t* out, dgs_stream_t stream);
+
+/* dgs_sad_matrix: a u32 [na,L], b u32 [nb,L] (L dwords per image, a multiple of 4; both 16-byte aligned; all four bytes of
+ * a dword count).  group == 0: out u64 [na,nb], out[i][j] = sum over the 4 L bytes of |a_i - b_j|.  group == m > 0 (nb must
+ * equal na m): out u64 [na,m], out[i][j] scores a_i against b_{i m + j}.
+ * First launch: a block takes DGS_SAD_TILE_A images of `a` (1 when grouped) and a tile of `b` over one chunk of
+ * DGS_SAD_CHUNK_DWORDS dwords -- 16-byte loads, the `a` quads in registers, every quad of `b` loaded once per a-tile,
+ * v_sad_u8 -- and stores one u32 partial per pair into tmp [chunk][row][column]; second launch: the 64-bit sums.  The
+ * number of blocks is a function of (na, nb, group, L) only; tmp's contents before the call do not matter.
+ * tmp >= dgs_sad_matrix_tmp_bytes(na, nb, L) bytes (0 for arguments the call refuses), 4-byte aligned; out 8-byte aligned.
+ * Refused before anything is enqueued: a NULL pointer, na or nb below 1, L below 4, no multiple of 4 or above 2^40, a negative
+ * group or nb != na group, a misaligned pointer, more than 2^31 - 1 blocks. */
+#define DGS_SAD_CHUNK_DWORDS 16384
+#define DGS_SAD_TILE_A 4
+size_t dgs_sad_matrix_tmp_bytes(int32_t na, int32_t nb, uint64_t L);
+int dgs_sad_matrix(const uint32_t* a, int32_t na, const uint32_t* b, int32_t nb, int32_t group, uint64_t L, uint64_t* out,
+                   void* tmp, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
