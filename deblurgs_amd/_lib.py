@@ -257,6 +257,12 @@ EXPORTS = {
     "dgs_sad_matrix_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64]),
     "dgs_sad_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_uint64] + [ctypes.c_void_p] * 3),
+    "dgs_resample_ksize": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
+    "dgs_resample_coeffs": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "dgs_resize_u8": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 6 +
+                      [ctypes.c_uint64, ctypes.c_void_p]),
+    "dgs_depth_bound_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32] +
+                             [ctypes.c_double] * 4 + [ctypes.c_void_p] * 3),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

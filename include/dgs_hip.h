@@ -845,6 +845,48 @@ size_t dgs_sad_matrix_tmp_bytes(int32_t na, int32_t nb, uint64_t L);
 int dgs_sad_matrix(const uint32_t* a, int32_t na, const uint32_t* b, int32_t nb, int32_t group, uint64_t L, uint64_t* out,
                    void* tmp, dgs_stream_t stream);
 
+/* ---- scene loading (additions to ABI 15; utils/general_utils.py:23-29 PILtoTorch, scene/dataset_readers.py:164-209) ----
+ * dgs_resample_ksize / dgs_resample_coeffs: HOST ONLY (no HIP call).  Pillow's precompute_coeffs + normalize_coeffs_8bpc
+ * for the antialiased bicubic filter (a = -0.5, support 2) on one axis, in double: scale = in / out, fs = max(scale, 1),
+ * support = 2 fs, ksize = (int)ceil(support) * 2 + 1 (what dgs_resample_ksize returns; 0 for sizes the call refuses).  Per
+ * output index xx: center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center +
+ * support + 0.5), in) - xmin, w[x] = bicubic((x + xmin - center + 0.5) (1 / fs)) for x < xmax, each divided by their
+ * sequential sum when that is not 0, kk[xx][x] = (int)(+-0.5 + w[x] 2^22) with the sign of w[x], the rest of the row 0;
+ * bounds[xx] = (xmin, xmax).  kk int32 [out, ksize] (kk_capacity: the int32 entries the caller's array holds), bounds int32
+ * [out, 2], both caller-owned HOST arrays.  Refused: a NULL pointer, a size outside 1..65536, in / out outside [1/64, 64],
+ * kk_capacity below out ksize. */
+int32_t dgs_resample_ksize(int32_t in_size, int32_t out_size);
+int dgs_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* kk, uint64_t kk_capacity, int32_t* bounds);
+
+/* dgs_resize_u8: Pillow's ImagingResample (Image.resize, BICUBIC) of G 8-bit images in one launch.  in u8 [G,H,W,C],
+ * pixel-interleaved as np.asarray(image) gives it, C = 1 or 3, any alignment.  kk_h / bounds_h: the DEVICE copies of
+ * dgs_resample_coeffs(W, w), kk_v / bounds_v of (H, h); the pair of an axis whose size does not change is not read (may be
+ * NULL) and that pass is skipped.  Horizontal pass first: every sample starts at 2^21, adds pixel * kk in 32-bit integers,
+ * >> 22 (arithmetic), clamped to 0..255 and ROUNDED TO A BYTE; then the vertical pass the same way on those bytes.
+ * Outputs, either may be NULL but not both: out_u8 u8 [G,h,w,C] (any alignment) and out_f32 float planar [C,h,w] per image,
+ * image g at out_f32 + g f32_image_stride floats (>= C h w: a caller writes straight into its slice of a larger stack),
+ * value (float)byte / 255.0f -- torch.from_numpy(u8) / 255.0 bit for bit.
+ * A block owns an output tile (16 x 64 pixels, shrunk where the input rows it needs do not fit 32 KiB of LDS), resamples
+ * those rows horizontally into LDS as bytes and runs the vertical pass out of LDS; no temporary, nothing kept between calls,
+ * no atomics: capturable.  Every index derived from the tables is clamped to the buffers.  Refused before anything is
+ * enqueued: a NULL input, both outputs NULL, G below 1, C outside {1, 3}, a size outside 1..65536, a ratio outside
+ * [1/64, 64] on an axis, a NULL table of an axis that is resampled, a table or out_f32 that is not 4-byte aligned, a float
+ * image stride below C h w, more than 2^31 - 1 blocks. */
+int dgs_resize_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t C, int32_t h, int32_t w, const int32_t* kk_h,
+                  const int32_t* bounds_h, const int32_t* kk_v, const int32_t* bounds_v, uint8_t* out_u8, float* out_f32,
+                  uint64_t f32_image_stride, dgs_stream_t stream);
+
+/* dgs_depth_bound_keys: the per-(camera, point) part of get_bds in double.  points double [n,3], w2c double [m,3,4] (rows
+ * of the world-to-camera matrix [R | t]), both on the device; w, h, fx, fy: the FIRST camera's, used for every camera as the
+ * reference does.  With cam = R p + t: u = cam.x / fx, v = cam.y / fy, d = cam.z - cam.x (w / 2) / fx - cam.y (h / 2) / fy,
+ * px = u / d, py = v / d (the reference multiplies the row vector by inv(K), not K: restated, not repaired); the pair
+ * counts when cam.z > 0.01 && 0 <= px < w && 0 <= py < h.  keys float [m,n]: (float)cam.z of a pair that counts, a quiet NaN
+ * otherwise (NaNs sort last in dgs_order_stats); counts u32 [m]: the pairs that count (zeroed by the call's first launch,
+ * then one integer atomicAdd per block).  Two launches, capturable.  Refused before anything is enqueued: a NULL pointer,
+ * n below 1, m outside 1..65535, a w, h, fx or fy that is not positive and finite, a misaligned pointer. */
+int dgs_depth_bound_keys(const double* points, int32_t n, const double* w2c, int32_t m, double w, double h, double fx,
+                         double fy, float* keys, uint32_t* counts, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
