@@ -261,6 +261,10 @@ EXPORTS = {
     "dgs_resample_coeffs": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "dgs_resize_u8": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 6 +
                       [ctypes.c_uint64, ctypes.c_void_p]),
+    "dgs_resize_rgba_u8": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 5 + [ctypes.c_void_p] * 6 +
+                           [ctypes.c_uint64, ctypes.c_void_p]),
+    "dgs_rgba_over_u8": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 2 +
+                         [ctypes.c_uint64, ctypes.c_void_p]),
     "dgs_depth_bound_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32] +
                              [ctypes.c_double] * 4 + [ctypes.c_void_p] * 3),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),

@@ -32,17 +32,34 @@
 //     This is a parity trap, not a projection; it is restated, not repaired.  Key = (float)cam.z of a counted pair, a quiet
 //     NaN otherwise (NaNs sort last in dgs_order_stats: the ranks below the count index exactly the counted depths); the
 //     counts are an integer sum (one atomicAdd of a block's popcount per block; the launcher's first kernel zeroes them).
+//   * dgs_resize_rgba_u8: Pillow's `Image.resize` of an RGBA image, which is NOT four independent channels: the image is
+//     converted to premultiplied alpha (RGBa: MULDIV255(c, a), t = c a + 128, ((t >> 8) + t) >> 8), the four bytes are
+//     resampled, and the result is converted back (colour copied where alpha is 0 or 255, else min(255, 255 c / a)).  The
+//     same kernel template with C = 4 and the alpha pixel policy: premultiplied where a pixel is LOADED (the horizontal
+//     pass, or the row copy when only the vertical pass runs), un-premultiplied where the result tile is STORED.  When no
+//     pass runs it is Pillow's plain copy: no round trip, the colour under alpha 0 survives.  LDS: 32 KiB of rows + 4 KiB of
+//     result tile (36 KiB a block: still four blocks a CU of 160 KiB); 128 rows of 64 pixels fit, so the tile shrinks from
+//     vertical ratios above ~6.6 on.
+//   * dgs_rgba_over_u8: the Blender reader's composite over black or white (scene/dataset_readers.py:335-341), per colour
+//     byte trunc(((c / 255.0) (a / 255.0) + bg (1.0 - a / 255.0)) 255.0) in IEEE double, one rounding per operation, in the
+//     reference's order (the `+ 0.0 (..)` of black included).  x / 255.0 comes from a 256-entry LDS table every block
+//     fills with one correctly rounded division per thread; the rest is three multiplications, a subtraction and an
+//     addition per byte.  A thread makes 4 consecutive pixels of the flat [G H W] pixel array (one 16-byte load where the
+//     input is 16-byte aligned, byte loads where it is not); a block stages its 1024 x 3 result bytes in LDS and stores
+//     them twice with neighbouring lanes on neighbouring addresses: as dwords (bytes where the output is misaligned) of
+//     the interleaved u8 [G,H,W,3], and as float planes [3,H,W] per image (byte / 255.0f).
 // No allocation, no host synchronisation, nothing kept between calls, no float atomics: capturable.
 #include "dgs_common.h"
 
 #include <math.h>
+#include <stdio.h>
 
 namespace {
 
 constexpr int RESIZE_PRECISION_BITS = 32 - 8 - 2;     // Pillow's PRECISION_BITS for 8-bit channels
 constexpr int RESIZE_ROWS_BYTES = 32768;              // LDS for the horizontally resampled rows of a tile
 constexpr int RESIZE_TH = 16, RESIZE_TW = 64;         // the default (largest) output tile
-constexpr int RESIZE_MAX_C = 3;
+constexpr int RESIZE_MAX_C = 4;
 constexpr int RESIZE_MAX_DIM = 65536;                 // per axis, input and output
 constexpr double RESIZE_MAX_RATIO = 64.0;
 
@@ -102,17 +119,31 @@ __device__ __forceinline__ int clip8(int v) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-template <int C>
+// Pillow's RGBA -> RGBa (premultiply) and RGBa -> RGBA conversions of one colour byte (Convert.c)
+__device__ __forceinline__ int premultiply8(int c, int alpha) {
+  const int t = c * alpha + 128;
+  return ((t >> 8) + t) >> 8;
+}
+__device__ __forceinline__ int unpremultiply8(int c, int alpha) {
+  if (alpha == 0 || alpha == 255) return c;
+  const int v = 255 * c / alpha;
+  return v > 255 ? 255 : v;
+}
+
+// ALPHA (C = 4 only): the fourth byte is an alpha the three others are premultiplied by while they are resampled
+template <int C, bool ALPHA>
 __global__ void __launch_bounds__(256)
 resize_u8_kernel(const ResizeArgs a) {
+  static_assert(C >= 1 && C <= RESIZE_MAX_C && (!ALPHA || C == 4), "channels");
   __shared__ uint8_t rows[RESIZE_ROWS_BYTES];
-  __shared__ uint8_t tile[RESIZE_TH * RESIZE_TW * RESIZE_MAX_C];
+  __shared__ uint8_t tile[RESIZE_TH * RESIZE_TW * C];
   const uint32_t tx = blockIdx.x % a.tiles_x;
   const uint32_t ty = (blockIdx.x / a.tiles_x) % a.tiles_y;
   const size_t g = blockIdx.x / (a.tiles_x * a.tiles_y);
   const int x0 = (int)tx * a.tw, y0 = (int)ty * a.th;
   const int nx = min(a.tw, a.w - x0), ny = min(a.th, a.h - y0);
   const bool do_h = a.kk_h != nullptr, do_v = a.kk_v != nullptr;
+  const bool premul = ALPHA && (do_h || do_v);                 // (neither pass: Pillow's plain copy)
 
   // the input rows this tile's vertical pass reads (the first taps of the bounds table do not decrease with the row)
   int r0 = y0, r1 = y0 + ny;
@@ -142,14 +173,29 @@ resize_u8_kernel(const ResizeArgs a) {
       for (int c = 0; c < C; c++) ss[c] = 1 << (RESIZE_PRECISION_BITS - 1);
       for (int t = 0; t < xmax; t++) {
         const int kt = k[t];
+        if constexpr (ALPHA) {
+          const int alpha = (int)p[t * C + C - 1];
 #pragma unroll
-        for (int c = 0; c < C; c++) ss[c] += (int)p[t * C + c] * kt;
+          for (int c = 0; c < C - 1; c++) ss[c] += premultiply8((int)p[t * C + c], alpha) * kt;
+          ss[C - 1] += alpha * kt;
+        } else {
+#pragma unroll
+          for (int c = 0; c < C; c++) ss[c] += (int)p[t * C + c] * kt;
+        }
       }
 #pragma unroll
       for (int c = 0; c < C; c++) dst[c] = (uint8_t)clip8(ss[c]);
     } else {
+      if (premul) {
+        const uint8_t* p = src + (size_t)(x0 + x) * (size_t)C;
+        const int alpha = (int)p[C - 1];
 #pragma unroll
-      for (int c = 0; c < C; c++) dst[c] = src[(size_t)(x0 + x) * (size_t)C + c];
+        for (int c = 0; c < C - 1; c++) dst[c] = (uint8_t)premultiply8((int)p[c], alpha);
+        dst[C - 1] = (uint8_t)alpha;
+      } else {
+#pragma unroll
+        for (int c = 0; c < C; c++) dst[c] = src[(size_t)(x0 + x) * (size_t)C + c];
+      }
     }
   }
   __syncthreads();
@@ -181,7 +227,11 @@ resize_u8_kernel(const ResizeArgs a) {
     uint8_t* dst = a.out_u8 + ((g * (size_t)a.h + (size_t)y0) * (size_t)a.w + (size_t)x0) * (size_t)C;
     for (int i = (int)threadIdx.x; i < ny * tile_pitch; i += 256) {
       const int y = i / tile_pitch, xc = i - y * tile_pitch;
-      dst[(size_t)y * (size_t)a.w * (size_t)C + xc] = tile[i];
+      uint8_t v = tile[i];
+      if constexpr (ALPHA) {      // (C = 4: the pixel's alpha is byte 3 of its dword)
+        if (premul && (i & 3) != 3) v = (uint8_t)unpremultiply8((int)v, (int)tile[i | 3]);
+      }
+      dst[(size_t)y * (size_t)a.w * (size_t)C + xc] = v;
     }
   }
   if (a.out_f32 != nullptr) {     // planar: item i = (channel, row, column), column fastest
@@ -190,8 +240,157 @@ resize_u8_kernel(const ResizeArgs a) {
     for (int i = (int)threadIdx.x; i < C * plane; i += 256) {
       const int c = i / plane, rem = i - c * plane;
       const int y = rem / nx, x = rem - y * nx;
-      dst[((size_t)c * (size_t)a.h + (size_t)(y0 + y)) * (size_t)a.w + (size_t)(x0 + x)] =
-          (float)tile[y * tile_pitch + x * C + c] / 255.0f;
+      uint8_t v = tile[y * tile_pitch + x * C + c];
+      if constexpr (ALPHA) {
+        if (premul && c != C - 1) v = (uint8_t)unpremultiply8((int)v, (int)tile[y * tile_pitch + x * C + C - 1]);
+      }
+      dst[((size_t)c * (size_t)a.h + (size_t)(y0 + y)) * (size_t)a.w + (size_t)(x0 + x)] = (float)v / 255.0f;
+    }
+  }
+}
+
+int resize_fail(const char* who, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  return dgs_fail_arg(msg);
+}
+
+// The argument checks, the tile choice and the launch shared by dgs_resize_u8 (C = 1 or 3; 0 stands for a refused channel
+// count) and dgs_resize_rgba_u8 (C = 4 with the alpha policy).
+int resize_call(const char* who, bool alpha, const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t C, int32_t h,
+                int32_t w, const int32_t* kk_h, const int32_t* bounds_h, const int32_t* kk_v, const int32_t* bounds_v,
+                uint8_t* out_u8, float* out_f32, uint64_t f32_image_stride, dgs_stream_t stream) {
+  if (in == nullptr) return resize_fail(who, "null input pointer");
+  if (out_u8 == nullptr && out_f32 == nullptr) return resize_fail(who, "both outputs are null");
+  if (G < 1) return resize_fail(who, "G must be at least 1");
+  if (C == 0) return resize_fail(who, "C must be 1 or 3");
+  if (H < 1 || W < 1 || h < 1 || w < 1 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || h > RESIZE_MAX_DIM || w > RESIZE_MAX_DIM)
+    return resize_fail(who, "sizes must be in 1..65536");
+  if (!ratio_ok(H, h) || !ratio_ok(W, w)) return resize_fail(who, "ratio outside [1/64, 64] on an axis");
+  if (W != w && (kk_h == nullptr || bounds_h == nullptr)) return resize_fail(who, "null horizontal table");
+  if (H != h && (kk_v == nullptr || bounds_v == nullptr)) return resize_fail(who, "null vertical table");
+  if (((reinterpret_cast<uintptr_t>(kk_h) | reinterpret_cast<uintptr_t>(bounds_h) | reinterpret_cast<uintptr_t>(kk_v) |
+        reinterpret_cast<uintptr_t>(bounds_v) | reinterpret_cast<uintptr_t>(out_f32)) & 3u) != 0)
+    return resize_fail(who, "the tables and the float output must be 4-byte aligned");
+  if (out_f32 != nullptr && f32_image_stride < (uint64_t)C * (uint64_t)h * (uint64_t)w)
+    return resize_fail(who, alpha ? "the float image stride is below 4 * h * w" : "the float image stride is below C * h * w");
+  ResizeArgs a;
+  a.in = in;
+  a.H = H, a.W = W, a.C = C, a.h = h, a.w = w;
+  a.kk_h = (W != w) ? kk_h : nullptr;
+  a.bounds_h = (W != w) ? bounds_h : nullptr;
+  a.kk_v = (H != h) ? kk_v : nullptr;
+  a.bounds_v = (H != h) ? bounds_v : nullptr;
+  a.ksize_h = axis_scale(W, w).ksize;
+  a.ksize_v = axis_scale(H, h).ksize;
+  // the largest tile whose rows fit the LDS: rows first (they cost recomputed taps), then columns
+  int th = RESIZE_TH, tw = RESIZE_TW;
+  while ((int64_t)rows_span(H, h, th) * tw * C > RESIZE_ROWS_BYTES) {
+    if (th > 1) th /= 2;
+    else if (tw > 1) tw /= 2;
+    else return resize_fail(who, "no tile fits the LDS budget");                 // (not reachable within the ratio limits)
+  }
+  a.th = th, a.tw = tw;
+  a.cap_rows = RESIZE_ROWS_BYTES / (tw * C);
+  a.tiles_x = (uint32_t)((w + tw - 1) / tw);
+  a.tiles_y = (uint32_t)((h + th - 1) / th);
+  const uint64_t blocks = (uint64_t)G * a.tiles_x * a.tiles_y;
+  if (blocks > 0x7fffffffull) return resize_fail(who, "more than 2^31 - 1 blocks");
+  a.out_u8 = out_u8;
+  a.out_f32 = out_f32;
+  a.image_stride = f32_image_stride;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (alpha)
+    hipLaunchKernelGGL((resize_u8_kernel<4, true>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+  else if (C == 3)
+    hipLaunchKernelGGL((resize_u8_kernel<3, false>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((resize_u8_kernel<1, false>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, who);
+}
+
+// ------------------------------------------------------------------------------------------- RGBA over a background
+constexpr int OVER_PIXELS = 4;                         // per thread: 16 input bytes
+constexpr int OVER_BLOCK_PIXELS = 256 * OVER_PIXELS;
+
+struct OverArgs {
+  const uint8_t* in;         // [n_pixels, 4]
+  uint64_t n_pixels;         // G H W
+  uint64_t plane;            // H W
+  double bg;                 // 0.0 or 1.0
+  uint8_t* out_u8;           // [n_pixels, 3] or nullptr
+  float* out_f32;            // [G] x image_stride floats, [3,H,W] each, or nullptr
+  uint64_t image_stride;
+};
+
+__global__ void __launch_bounds__(256)
+rgba_over_kernel(const OverArgs a) {
+  __shared__ double unit[256];                         // x / 255.0
+  __shared__ uint32_t stage[OVER_BLOCK_PIXELS * 3 / 4];      // the block's result bytes, pixel-interleaved
+  const uint32_t t = threadIdx.x;
+  unit[t] = (double)t / 255.0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blockIdx.x * (uint64_t)OVER_BLOCK_PIXELS;
+  const uint64_t p0 = base + (uint64_t)t * OVER_PIXELS;
+  uint32_t px[OVER_PIXELS] = {0u, 0u, 0u, 0u};
+  if (p0 + OVER_PIXELS <= a.n_pixels && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) {
+    const uint4 q = *reinterpret_cast<const uint4*>(a.in + p0 * 4);
+    px[0] = q.x, px[1] = q.y, px[2] = q.z, px[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < OVER_PIXELS; j++) {
+      if (p0 + j < a.n_pixels) {
+        const uint8_t* p = a.in + (p0 + j) * 4;
+        px[j] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+      }
+    }
+  }
+  uint32_t packed[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < OVER_PIXELS; j++) {
+    const double alpha = unit[px[j] >> 24];
+    const double rest = a.bg * (1.0 - alpha);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const double v = (unit[(px[j] >> (8 * c)) & 255u] * alpha + rest) * 255.0;
+      const uint32_t byte = (uint32_t)(int)v & 255u;   // np.byte: truncation toward zero, the low byte kept
+      const int k = 3 * j + c;
+      packed[k >> 2] |= byte << (8 * (k & 3));
+    }
+  }
+  stage[3 * t + 0] = packed[0], stage[3 * t + 1] = packed[1], stage[3 * t + 2] = packed[2];
+  __syncthreads();
+  if (base >= a.n_pixels) return;
+  const uint64_t left = a.n_pixels - base;
+  const uint32_t npix = left < (uint64_t)OVER_BLOCK_PIXELS ? (uint32_t)left : (uint32_t)OVER_BLOCK_PIXELS;
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(stage);
+  if (a.out_u8 != nullptr) {
+    uint8_t* dst = a.out_u8 + base * 3;                // (base * 3 is a multiple of 4)
+    const uint32_t nbytes = npix * 3u;
+    if ((reinterpret_cast<uintptr_t>(a.out_u8) & 3u) == 0) {
+      for (uint32_t i = t; i * 4u < nbytes; i += 256u) {
+        if (i * 4u + 4u <= nbytes) {
+          reinterpret_cast<uint32_t*>(dst)[i] = stage[i];
+        } else {
+          for (uint32_t b = i * 4u; b < nbytes; b++) dst[b] = bytes[b];
+        }
+      }
+    } else {
+      for (uint32_t i = t; i < nbytes; i += 256u) dst[i] = bytes[i];
+    }
+  }
+  if (a.out_f32 != nullptr) {     // planar: lane t takes pixel t, t + 256, ... of the block, one plane after the other
+#pragma unroll
+    for (int k = 0; k < OVER_PIXELS; k++) {
+      const uint32_t q = (uint32_t)k * 256u + t;
+      if (q < npix) {
+        const uint64_t p = base + q;
+        const uint64_t g = p / a.plane, rem = p - g * a.plane;
+        float* dst = a.out_f32 + g * a.image_stride + rem;
+#pragma unroll
+        for (int c = 0; c < 3; c++) dst[(uint64_t)c * a.plane] = (float)bytes[q * 3u + (uint32_t)c] / 255.0f;
+      }
     }
   }
 }
@@ -280,52 +479,41 @@ int dgs_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* kk, uint64_t
 int dgs_resize_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t C, int32_t h, int32_t w, const int32_t* kk_h,
                   const int32_t* bounds_h, const int32_t* kk_v, const int32_t* bounds_v, uint8_t* out_u8, float* out_f32,
                   uint64_t f32_image_stride, dgs_stream_t stream) {
-  if (in == nullptr) return dgs_fail_arg("resize_u8: null input pointer");
-  if (out_u8 == nullptr && out_f32 == nullptr) return dgs_fail_arg("resize_u8: both outputs are null");
-  if (G < 1) return dgs_fail_arg("resize_u8: G must be at least 1");
-  if (C != 1 && C != 3) return dgs_fail_arg("resize_u8: C must be 1 or 3");
-  if (H < 1 || W < 1 || h < 1 || w < 1 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || h > RESIZE_MAX_DIM || w > RESIZE_MAX_DIM)
-    return dgs_fail_arg("resize_u8: sizes must be in 1..65536");
-  if (!ratio_ok(H, h) || !ratio_ok(W, w)) return dgs_fail_arg("resize_u8: ratio outside [1/64, 64] on an axis");
-  if (W != w && (kk_h == nullptr || bounds_h == nullptr)) return dgs_fail_arg("resize_u8: null horizontal table");
-  if (H != h && (kk_v == nullptr || bounds_v == nullptr)) return dgs_fail_arg("resize_u8: null vertical table");
-  if (((reinterpret_cast<uintptr_t>(kk_h) | reinterpret_cast<uintptr_t>(bounds_h) | reinterpret_cast<uintptr_t>(kk_v) |
-        reinterpret_cast<uintptr_t>(bounds_v) | reinterpret_cast<uintptr_t>(out_f32)) & 3u) != 0)
-    return dgs_fail_arg("resize_u8: the tables and the float output must be 4-byte aligned");
-  if (out_f32 != nullptr && f32_image_stride < (uint64_t)C * (uint64_t)h * (uint64_t)w)
-    return dgs_fail_arg("resize_u8: the float image stride is below C * h * w");
-  ResizeArgs a;
+  return resize_call("resize_u8", false, in, G, H, W, (C == 1 || C == 3) ? C : 0, h, w, kk_h, bounds_h, kk_v, bounds_v, out_u8,
+                     out_f32, f32_image_stride, stream);
+}
+
+int dgs_resize_rgba_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t h, int32_t w, const int32_t* kk_h,
+                       const int32_t* bounds_h, const int32_t* kk_v, const int32_t* bounds_v, uint8_t* out_u8, float* out_f32,
+                       uint64_t f32_image_stride, dgs_stream_t stream) {
+  return resize_call("resize_rgba_u8", true, in, G, H, W, 4, h, w, kk_h, bounds_h, kk_v, bounds_v, out_u8, out_f32,
+                     f32_image_stride, stream);
+}
+
+int dgs_rgba_over_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t white, uint8_t* out_u8, float* out_f32,
+                     uint64_t f32_image_stride, dgs_stream_t stream) {
+  if (in == nullptr) return dgs_fail_arg("rgba_over_u8: null input pointer");
+  if (out_u8 == nullptr && out_f32 == nullptr) return dgs_fail_arg("rgba_over_u8: both outputs are null");
+  if (G < 1) return dgs_fail_arg("rgba_over_u8: G must be at least 1");
+  if (H < 1 || W < 1 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM) return dgs_fail_arg("rgba_over_u8: sizes must be in 1..65536");
+  if ((reinterpret_cast<uintptr_t>(out_f32) & 3u) != 0)
+    return dgs_fail_arg("rgba_over_u8: the float output must be 4-byte aligned");
+  const uint64_t plane = (uint64_t)H * (uint64_t)W;
+  if (out_f32 != nullptr && f32_image_stride < 3 * plane)
+    return dgs_fail_arg("rgba_over_u8: the float image stride is below 3 * H * W");
+  OverArgs a;
   a.in = in;
-  a.H = H, a.W = W, a.C = C, a.h = h, a.w = w;
-  a.kk_h = (W != w) ? kk_h : nullptr;
-  a.bounds_h = (W != w) ? bounds_h : nullptr;
-  a.kk_v = (H != h) ? kk_v : nullptr;
-  a.bounds_v = (H != h) ? bounds_v : nullptr;
-  a.ksize_h = axis_scale(W, w).ksize;
-  a.ksize_v = axis_scale(H, h).ksize;
-  // the largest tile whose rows fit the LDS: rows first (they cost recomputed taps), then columns
-  int th = RESIZE_TH, tw = RESIZE_TW;
-  while ((int64_t)rows_span(H, h, th) * tw * C > RESIZE_ROWS_BYTES) {
-    if (th > 1) th /= 2;
-    else if (tw > 1) tw /= 2;
-    else return dgs_fail_arg("resize_u8: no tile fits the LDS budget");          // (not reachable within the ratio limits)
-  }
-  a.th = th, a.tw = tw;
-  a.cap_rows = RESIZE_ROWS_BYTES / (tw * C);
-  a.tiles_x = (uint32_t)((w + tw - 1) / tw);
-  a.tiles_y = (uint32_t)((h + th - 1) / th);
-  const uint64_t blocks = (uint64_t)G * a.tiles_x * a.tiles_y;
-  if (blocks > 0x7fffffffull) return dgs_fail_arg("resize_u8: more than 2^31 - 1 blocks");
+  a.n_pixels = (uint64_t)G * plane;
+  a.plane = plane;
+  a.bg = white != 0 ? 1.0 : 0.0;
   a.out_u8 = out_u8;
   a.out_f32 = out_f32;
   a.image_stride = f32_image_stride;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (C == 3)
-    hipLaunchKernelGGL(resize_u8_kernel<3>, dim3((uint32_t)blocks), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(resize_u8_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, st, a);
+  const uint64_t blocks = (a.n_pixels + OVER_BLOCK_PIXELS - 1) / OVER_BLOCK_PIXELS;
+  if (blocks > 0x7fffffffull) return dgs_fail_arg("rgba_over_u8: more than 2^31 - 1 blocks");
+  hipLaunchKernelGGL(rgba_over_kernel, dim3((uint32_t)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "resize_u8");
+  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "rgba_over_u8");
 }
 
 int dgs_depth_bound_keys(const double* points, int32_t n, const double* w2c, int32_t m, double w, double h, double fx,

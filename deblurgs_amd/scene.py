@@ -11,6 +11,11 @@ trains on.  The counterpart of the reference's readColmapSceneInfo (scene/datase
     nerfpp_radius          getNerfppNorm's radius
     random_frustum_points  random_pcd_init, drawing from numpy's global generator in the reference's order
     load_colmap_scene      the directory -> a SceneData
+    rgba_over              readCamerasFromTransforms' float64 composite of RGBA over black / white (dgs_rgba_over_u8)
+    resize_rgba_images     Pillow's RGBA `Image.resize`: premultiplied, resampled, un-premultiplied (dgs_resize_rgba_u8)
+    read_blender_cameras   readCamerasFromTransforms' cameras of a transforms_*.json
+    load_blender_scene     readNerfSyntheticInfo: a NeRF-synthetic ("Blender") directory -> a SceneData
+    load_scene             the reader the reference's Scene picks for a directory
 
         scene = load_colmap_scene(path, resolution=2)
         motion, cloud = scene.motion_module(), scene.cloud()
@@ -104,18 +109,33 @@ def resize_images(images_u8, size, out=None, out_u8=None):
                  slice of a larger stack: images may be any stride >= C h w apart, each image itself contiguous.
         out_u8   uint8 [G,h,w,C], contiguous, to write the resized bytes into.
     Neither given: a new float tensor is returned.  One given: it is written and returned.  Both: (out, out_u8)."""
-    if not torch.is_tensor(images_u8):
-        raise RuntimeError("resize_images needs a tensor on a HIP device (no CPU fallback)")
-    _need_cuda(images_u8.device, "resize_images")
-    single = images_u8.dim() == 3
-    if single:
-        images_u8 = images_u8[None]
-    if images_u8.dim() != 4 or images_u8.dtype != torch.uint8:
-        raise ValueError("resize_images takes a uint8 [G,H,W,C] tensor")
-    images_u8 = images_u8.contiguous()
+    images_u8, single = _images_arg(images_u8, "resize_images")
     G, H, W, C = (int(v) for v in images_u8.shape)
     w, h = int(size[0]), int(size[1])
     dev = images_u8.device
+    out, stride = _outputs_arg(single, G, C, h, w, dev, out, out_u8)
+    L = _lib.lib()
+    tables = _resize_tables(H, W, h, w, dev)
+    _lib.check(L.dgs_resize_u8(_ptr(images_u8), G, H, W, C, h, w, *tables, _ptr(out_u8), _ptr(out), stride, _stream(dev)),
+               "dgs_resize_u8")
+    return _outputs_result(out, out_u8)
+
+
+def _images_arg(images_u8, who, channels=None):
+    """(contiguous uint8 [G,H,W,C] on a HIP device, whether a single [H,W,C] image was given)."""
+    if not torch.is_tensor(images_u8):
+        raise RuntimeError(f"{who} needs a tensor on a HIP device (no CPU fallback)")
+    _need_cuda(images_u8.device, who)
+    single = images_u8.dim() == 3
+    if single:
+        images_u8 = images_u8[None]
+    if images_u8.dim() != 4 or images_u8.dtype != torch.uint8 or (channels is not None and images_u8.shape[3] != channels):
+        raise ValueError(f"{who} takes a uint8 [G,H,W,{'C' if channels is None else channels}] tensor")
+    return images_u8.contiguous(), single
+
+
+def _outputs_arg(single, G, C, h, w, dev, out, out_u8):
+    """The output rules the image kernels share: (out, image stride in floats); a new float tensor when neither is given."""
     if out is None and out_u8 is None:
         out = torch.empty((G, C, max(h, 0), max(w, 0)), dtype=torch.float32, device=dev)
     stride = 0
@@ -128,24 +148,59 @@ def resize_images(images_u8, size, out=None, out_u8=None):
     if out_u8 is not None:
         if out_u8.dtype != torch.uint8 or out_u8.numel() != G * h * w * C or not out_u8.is_contiguous() or out_u8.device != dev:
             raise ValueError(f"out_u8 must be a contiguous uint8 tensor of {G} x {h} x {w} x {C} bytes on the images' device")
+    return out, stride
+
+
+def _outputs_result(out, out_u8):
+    if out is not None and out_u8 is not None:
+        return out, out_u8
+    return out if out is not None else out_u8
+
+
+def _resize_tables(H, W, h, w, dev):
+    """The four table pointers of a resize call (0 for an axis that keeps its size or that the call will refuse)."""
     L = _lib.lib()
     kk_h = b_h = kk_v = b_v = None
     if W != w and L.dgs_resample_ksize(W, w) > 0:
         kk_h, b_h = _device_tables(W, w, dev)
     if H != h and L.dgs_resample_ksize(H, h) > 0:
         kk_v, b_v = _device_tables(H, h, dev)
-    _lib.check(L.dgs_resize_u8(_ptr(images_u8), G, H, W, C, h, w, _ptr(kk_h), _ptr(b_h), _ptr(kk_v), _ptr(b_v), _ptr(out_u8),
-                               _ptr(out), stride, _stream(dev)), "dgs_resize_u8")
-    if out is not None and out_u8 is not None:
-        return out, out_u8
-    return out if out is not None else out_u8
+    return _ptr(kk_h), _ptr(b_h), _ptr(kk_v), _ptr(b_v)
+
+
+def resize_rgba_images(images_u8, size, out=None, out_u8=None):
+    """Pillow's `Image.resize(size)` of RGBA images on the device, byte for byte (dgs_resize_rgba_u8): premultiplied by
+    alpha, resampled, un-premultiplied -- and a plain copy when the size does not change.  images_u8: uint8 [G,H,W,4] (or
+    [H,W,4]); out float32 [G,4,h,w] / out_u8 uint8 [G,h,w,4] under resize_images' rules."""
+    images_u8, single = _images_arg(images_u8, "resize_rgba_images", 4)
+    G, H, W, _ = (int(v) for v in images_u8.shape)
+    w, h = int(size[0]), int(size[1])
+    dev = images_u8.device
+    out, stride = _outputs_arg(single, G, 4, h, w, dev, out, out_u8)
+    tables = _resize_tables(H, W, h, w, dev)
+    _lib.check(_lib.lib().dgs_resize_rgba_u8(_ptr(images_u8), G, H, W, h, w, *tables, _ptr(out_u8), _ptr(out), stride,
+                                             _stream(dev)), "dgs_resize_rgba_u8")
+    return _outputs_result(out, out_u8)
+
+
+def rgba_over(images_u8, white_background, out=None, out_u8=None):
+    """The Blender reader's composite of RGBA images over a white or black background on the device (dgs_rgba_over_u8):
+    per colour byte numpy's float64 `(c/255 * a/255 + bg * (1 - a/255)) * 255` cast to np.byte, bit for bit.  images_u8:
+    uint8 [G,H,W,4] (or [H,W,4]); out float32 [G,3,H,W] (byte / 255) / out_u8 uint8 [G,H,W,3] under resize_images' rules."""
+    images_u8, single = _images_arg(images_u8, "rgba_over", 4)
+    G, H, W, _ = (int(v) for v in images_u8.shape)
+    dev = images_u8.device
+    out, stride = _outputs_arg(single, G, 3, H, W, dev, out, out_u8)
+    _lib.check(_lib.lib().dgs_rgba_over_u8(_ptr(images_u8), G, H, W, 1 if white_background else 0, _ptr(out_u8), _ptr(out),
+                                           stride, _stream(dev)), "dgs_rgba_over_u8")
+    return _outputs_result(out, out_u8)
 
 
 def pil_to_torch(image_u8, size, device="cuda"):
     """PILtoTorch (utils/general_utils.py:23-29) of one 8-bit image: float32 [C,h,w] on the device, resized to size = (w, h)
-    and divided by 255.  image_u8: uint8 [H,W] (mode L) or [H,W,C] as np.asarray(PIL image) gives it.  L and RGB are resized
-    on the device; Pillow resizes the other 8-bit modes differently (LA and RGBA go through premultiplied alpha), so those
-    take PIL's own `resize` on the host when PIL is importable and raise otherwise."""
+    and divided by 255.  image_u8: uint8 [H,W] (mode L) or [H,W,C] as np.asarray(PIL image) gives it.  L, RGB and RGBA are
+    resized on the device (RGBA through premultiplied alpha, as Pillow does: resize_rgba_images); LA goes through
+    premultiplied alpha too and takes PIL's own `resize` on the host when PIL is importable, and raises otherwise."""
     _need_cuda(device, "pil_to_torch")
     arr = image_u8.cpu().numpy() if torch.is_tensor(image_u8) else np.asarray(image_u8)
     if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
@@ -153,16 +208,16 @@ def pil_to_torch(image_u8, size, device="cuda"):
     if arr.ndim == 2:
         arr = arr[:, :, None]
     C = arr.shape[2]
-    if C in (1, 3):
+    if C in (1, 3, 4):
         src = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
-        return resize_images(src, size)[0]
-    if C not in (2, 4):
+        return (resize_rgba_images if C == 4 else resize_images)(src, size)[0]
+    if C != 2:
         raise ValueError(f"pil_to_torch: an 8-bit image has 1 to 4 channels, not {C}")
     try:
         from PIL import Image
     except ImportError:
-        raise RuntimeError(f"pil_to_torch: a {C}-channel image ({'LA' if C == 2 else 'RGBA'}) is resized through premultiplied "
-                           "alpha by Pillow; that path runs on the host and needs PIL, which is not importable") from None
+        raise RuntimeError("pil_to_torch: a 2-channel image (LA) is resized through premultiplied alpha by Pillow; that path "
+                           "runs on the host and needs PIL, which is not importable") from None
     resized = np.array(Image.fromarray(np.ascontiguousarray(arr)).resize((int(size[0]), int(size[1]))))
     return (torch.from_numpy(resized) / 255.0).permute(2, 0, 1).contiguous().to(device)
 
@@ -406,7 +461,7 @@ def _ply_round_trip(xyz, rgb255):
 
 @dataclass
 class SceneData:
-    """What load_colmap_scene returns.
+    """What load_colmap_scene and load_blender_scene return.
         ref_cam         motion.RefCamera of the training size and the training cameras' field of view
         gt_images       float32 [n,3,h,w] on the device
         init_c2w        (rotations float64 [n,3,3], positions float64 [n,3]): CameraMotionModule(init_c2w=...)'s form
@@ -431,6 +486,7 @@ class SceneData:
     z_near: float = 0.2
     z_far: float = 100.0
     device: Any = "cuda"
+    white_background: bool = False      # the background the images were composited over (TrainingLoop's white_background)
 
     def motion_module(self, **kw):
         """CameraMotionModule on this scene's images and initial poses (kw: curve_order, num_subframes, ...)."""
@@ -464,7 +520,9 @@ def _find_image(path):
 
 
 def _load_images(cams, resolution, reader, device, what):
-    """float32 [n,3,h,w] on the device: every image read, uploaded and resized in groups of at most UPLOAD_BUDGET_BYTES."""
+    """float32 [n,3,h,w] on the device: every image read, uploaded and resized in groups of at most UPLOAD_BUDGET_BYTES.
+    A group holds images of one channel count; RGBA images are resized through premultiplied alpha (resize_rgba_images)
+    and their first three planes are the ground truth, as in loadCam."""
     if not cams:
         return None
     stack, size, src_shape, pending = None, None, None, []
@@ -472,7 +530,10 @@ def _load_images(cams, resolution, reader, device, what):
     def flush(first):
         if pending:
             src = torch.from_numpy(np.stack(pending)).to(device)
-            resize_images(src, size, out=stack[first:first + len(pending)])
+            if src.shape[3] == 4:
+                stack[first:first + len(pending)] = resize_rgba_images(src, size)[:, :3]
+            else:
+                resize_images(src, size, out=stack[first:first + len(pending)])
             pending.clear()
 
     first = 0
@@ -482,19 +543,17 @@ def _load_images(cams, resolution, reader, device, what):
             raise ValueError(f"{cam.image_path}: the image reader must return uint8 [H,W,C], got {img.dtype} {img.shape}")
         if img.ndim == 2:
             img = img[:, :, None]
+        if img.shape[2] not in (3, 4):
+            raise ValueError(f"{cam.image_path}: {what} images must be RGB (or RGBA), got {img.shape[2]} channel(s)")
         if src_shape is None:
-            src_shape = img.shape
+            src_shape = img.shape[:2]
             size = training_resolution(img.shape[1], img.shape[0], resolution)
-            if img.shape[2] not in (3, 4):
-                raise ValueError(f"{cam.image_path}: {what} images must be RGB (or RGBA), got {img.shape[2]} channel(s)")
             stack = torch.empty((len(cams), 3, size[1], size[0]), dtype=torch.float32, device=device)
-        elif img.shape != src_shape:
-            raise ValueError(f"{what} images must share one size: {cam.image_path} is {img.shape}, the first is {src_shape}")
-        if img.shape[2] == 4:           # Pillow's premultiplied-alpha path (host); the colour channels are the ground truth
+        elif img.shape[:2] != src_shape:
+            raise ValueError(f"{what} images must share one size: {cam.image_path} is {img.shape[:2]}, the first is {src_shape}")
+        if pending and pending[0].shape[2] != img.shape[2]:
             flush(first)
-            stack[i] = pil_to_torch(img, size, device)[:3]
-            first = i + 1
-            continue
+            first = i
         pending.append(np.ascontiguousarray(img))
         if len(pending) * img.size >= UPLOAD_BUDGET_BYTES:
             flush(first)
@@ -550,3 +609,202 @@ def load_colmap_scene(source_path, images="images", resolution=-1, eval=False, l
                      test_images=tests, test_c2w=_c2w_of(test) if test else None, points=points, colors=colors,
                      cameras_extent=float(radius), test_names=[c.image_name for c in test], train_cameras=train,
                      test_cameras=test, activation=activation, z_near=z_near, z_far=z_far, device=device)
+
+
+# ------------------------------------------------------------------------------------------------- Blender scenes
+def _rgba_of(img, path):
+    """uint8 [H,W,3] or [H,W,4] of what a reader returned: PIL's lossless `convert("RGBA")` of L and LA on the host (the
+    grey replicated), RGB and RGBA as they are (RGB has alpha 255, over which the composite is the identity)."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError(f"{path}: the image reader must return uint8 [H,W,C], got {img.dtype} {img.shape}")
+    if img.ndim == 2:
+        img = img[:, :, None]
+    C = img.shape[2]
+    if C == 1:
+        return np.repeat(img, 3, axis=2)
+    if C == 2:
+        return np.concatenate([np.repeat(img[:, :, :1], 3, axis=2), img[:, :, 1:]], axis=2)
+    if C not in (3, 4):
+        raise ValueError(f"{path}: an 8-bit image has 1 to 4 channels, not {C}")
+    return np.ascontiguousarray(img)
+
+
+def _read_blender(path, transformsfile, extension, reader):
+    """(CameraInfo list, the images as uint8 [H,W,3|4] arrays) of a transforms file, in the file's order."""
+    import json
+    with open(os.path.join(path, transformsfile)) as f:
+        contents = json.load(f)
+    fovx = contents["camera_angle_x"]
+    cams, images = [], []
+    for idx, frame in enumerate(contents["frames"]):
+        cam_name = frame["file_path"] + extension
+        c2w = np.array(frame["transform_matrix"])
+        c2w[:3, 1:3] *= -1                                  # OpenGL / Blender axes (y up, z back) -> COLMAP's (y down, z forward)
+        w2c = np.linalg.inv(c2w)
+        R = np.transpose(w2c[:3, :3])
+        T = w2c[:3, 3]
+        image_path = os.path.join(path, cam_name)
+        img = _rgba_of(reader(_find_image(image_path)), image_path)
+        height, width = int(img.shape[0]), int(img.shape[1])
+        fovy = focal2fov(fov2focal(fovx, width), height)
+        name = os.path.splitext(os.path.basename(cam_name))[0]
+        cams.append(CameraInfo(idx, R, T, fovy, fovx, image_path, name, width, height))
+        images.append(img)
+    return cams, images
+
+
+def read_blender_cameras(path, transformsfile, extension=".png", image_reader=None):
+    """The CameraInfo list of a NeRF-synthetic transforms file (readCamerasFromTransforms, scene/dataset_readers.py:310-350):
+    the frame's camera-to-world matrix with its y and z columns negated, inverted; R the transposed rotation of that, T its
+    translation; FovX the file's camera_angle_x, FovY from the focal length of FovX and the image's size (each image is
+    read for it); image_name the stem of file_path + extension; uid the frame's index."""
+    return _read_blender(path, transformsfile, extension, default_image_reader if image_reader is None else image_reader)[0]
+
+
+def split_blender(train, test, eval=False):
+    """(train, test) as readNerfSyntheticInfo splits them: without eval the test views are appended to the training views."""
+    return (list(train), list(test)) if eval else (list(train) + list(test), [])
+
+
+def blender_random_cloud(train_cams, num_points=100_000):
+    """(xyz float64 [n,3], rgb float64 [n,3] in 0..255) of readNerfSyntheticInfo's random initialisation: random_pcd_init
+    between the depths 2 and 8, THEN np.random.random((num_points, 3)) / 255 through SH2RGB, times 255 as storePly receives
+    it -- both from numpy's global generator, in this order."""
+    xyz = random_frustum_points(train_cams, near=2.0, far=8.0, num_pcd=num_points)
+    shs = np.random.random((num_points, 3)) / 255.0
+    return xyz, ((shs * C0 + 0.5) * 255)[:xyz.shape[0]]
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply_points(path):
+    """(xyz [n,3], rgb [n,3] in 0..255) of the vertex element of a PLY file in storePly's layout (x y z nx ny nz red green
+    blue; any scalar properties are accepted, lists are not): binary little- or big-endian, or ascii."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, count, props, in_vertex, first_element = None, None, [], False, None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: the PLY header does not end")
+            words = line.decode("ascii").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words[0] == "format":
+                fmt = words[1]
+            elif words[0] == "element":
+                first_element = words[1] if first_element is None else first_element
+                in_vertex = words[1] == "vertex"
+                if in_vertex:
+                    count = int(words[2])
+            elif words[0] == "property" and in_vertex:
+                if words[1] == "list" or words[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: unsupported vertex property {' '.join(words[1:])}")
+                props.append((words[2], _PLY_TYPES[words[1]]))
+            elif words[0] == "end_header":
+                break
+        if count is None or first_element != "vertex":
+            raise ValueError(f"{path}: the first element of the PLY file must be its vertices")
+        if fmt == "ascii":
+            rows = np.loadtxt(f, max_rows=count, ndmin=2) if count else np.zeros((0, len(props)))
+            data = {name: rows[:, k].astype(t) for k, (name, t) in enumerate(props)}
+        elif fmt in ("binary_little_endian", "binary_big_endian"):
+            order = "<" if fmt == "binary_little_endian" else ">"
+            data = np.frombuffer(f.read(), dtype=np.dtype([(name, order + t) for name, t in props]), count=count)
+        else:
+            raise ValueError(f"{path}: unknown PLY format {fmt}")
+    missing = [k for k in ("x", "y", "z", "red", "green", "blue") if k not in dict(props)]
+    if missing:
+        raise ValueError(f"{path}: the vertices have no {', '.join(missing)}")
+    return (np.vstack([data["x"], data["y"], data["z"]]).T, np.vstack([data["red"], data["green"], data["blue"]]).T)
+
+
+def _load_blender_images(images, white_background, resolution, device, what):
+    """float32 [n,3,h,w] on the device of the uint8 [H,W,3|4] arrays: uploaded in groups of one channel count and at most
+    UPLOAD_BUDGET_BYTES, RGBA composited over the background (rgba_over), then resized to training_resolution's size
+    (resize_images) -- one launch where the size does not change, two with a 3 byte / pixel intermediate where it does."""
+    if not images:
+        return None
+    H, W = images[0].shape[:2]
+    for k, img in enumerate(images):
+        if img.shape[:2] != (H, W):
+            raise ValueError(f"{what} images must share one size: image {k} is {img.shape[:2]}, the first is {(H, W)}")
+    size = training_resolution(W, H, resolution)
+    stack = torch.empty((len(images), 3, size[1], size[0]), dtype=torch.float32, device=device)
+    first = 0
+    while first < len(images):
+        C = images[first].shape[2]
+        last = first
+        while last < len(images) and images[last].shape[2] == C and (last - first) * H * W * C < UPLOAD_BUDGET_BYTES:
+            last += 1
+        src = torch.from_numpy(np.stack(images[first:last])).to(device)
+        out = stack[first:last]
+        if C == 3:
+            resize_images(src, size, out=out)
+        elif size == (W, H):
+            rgba_over(src, white_background, out=out)
+        else:
+            resize_images(rgba_over(src, white_background, out_u8=torch.empty((last - first, H, W, 3), dtype=torch.uint8,
+                                                                               device=device)), size, out=out)
+        first = last
+    return stack
+
+
+def load_blender_scene(source_path, white_background=False, eval=False, resolution=-1, extension=".png", activation="relu",
+                       z_near=0.2, z_far=100.0, device="cuda", image_reader=None, num_random_points=100_000):
+    """readNerfSyntheticInfo + cameraList_from_camInfos for a NeRF-synthetic ("Blender") directory: a SceneData.
+    source_path holds transforms_train.json and transforms_test.json; a frame's picture is file_path + extension.
+        white_background  composite the RGBA pictures over white instead of black (on the device, rgba_over: numpy's float64
+                          expression and its truncating cast, bit for bit); RGB pictures are taken as they are
+        eval              keep the test views apart; otherwise they are appended to the training views
+        resolution        loadCam's rule (training_resolution), applied to the composited bytes
+        points            source_path/points3d.ply when it exists (storePly's vertex layout); otherwise num_random_points
+                          (the reference: 100 000) from blender_random_cloud, drawn from numpy's global generator.  Both
+                          go through the float32 / uint8 quantisation of the reference's ply round trip; nothing is written.
+    The scene radius comes from the cameras alone.  The pictures must share one size."""
+    from .motion import RefCamera
+    _need_cuda(device, "load_blender_scene")
+    reader = default_image_reader if image_reader is None else image_reader
+    train, train_images = _read_blender(source_path, "transforms_train.json", extension, reader)
+    test, test_images = _read_blender(source_path, "transforms_test.json", extension, reader)
+    if not eval:
+        train_images, test_images = train_images + test_images, []
+    train, test = split_blender(train, test, eval)
+    if not train:
+        raise ValueError(f"{source_path}: no training camera")
+    first = train[0]
+    for c in train[1:]:
+        if (c.width, c.height, c.FovX, c.FovY) != (first.width, first.height, first.FovX, first.FovY):
+            raise ValueError(f"the training cameras must share one set of intrinsics: {c.image_name} has "
+                             f"{(c.width, c.height, c.FovX, c.FovY)}, {first.image_name} has "
+                             f"{(first.width, first.height, first.FovX, first.FovY)}")
+    ply = os.path.join(source_path, "points3d.ply")
+    xyz, rgb = read_ply_points(ply) if os.path.exists(ply) else blender_random_cloud(train, num_random_points)
+    points, colors = _ply_round_trip(xyz, rgb)
+    radius = nerfpp_radius(camera_centers(train))
+    white_background = bool(white_background)
+    gt = _load_blender_images(train_images, white_background, resolution, device, "training")
+    tests = _load_blender_images(test_images, white_background, resolution, device, "test")
+    h, w = int(gt.shape[2]), int(gt.shape[3])
+    ref = RefCamera(w, h, first.FovX, first.FovY, device=device)
+    return SceneData(ref_cam=ref, gt_images=gt, init_c2w=_c2w_of(train), image_names=[c.image_name for c in train],
+                     test_images=tests, test_c2w=_c2w_of(test) if test else None, points=points, colors=colors,
+                     cameras_extent=float(radius), test_names=[c.image_name for c in test], train_cameras=train,
+                     test_cameras=test, activation=activation, z_near=z_near, z_far=z_far, device=device,
+                     white_background=white_background)
+
+
+def load_scene(source_path, **kw):
+    """The loader the reference's Scene picks (scene/__init__.py:50-56): a `sparse` directory or `poses_bounds.npy` means a
+    COLMAP dataset (load_colmap_scene), `transforms_train.json` a Blender one (load_blender_scene); kw goes to that loader."""
+    if os.path.exists(os.path.join(source_path, "sparse")) or os.path.exists(os.path.join(source_path, "poses_bounds.npy")):
+        return load_colmap_scene(source_path, **kw)
+    if os.path.exists(os.path.join(source_path, "transforms_train.json")):
+        return load_blender_scene(source_path, **kw)
+    raise ValueError(f"{source_path}: neither a COLMAP dataset (sparse/, poses_bounds.npy) nor a Blender one "
+                     "(transforms_train.json): could not recognise the scene type")

@@ -876,6 +876,31 @@ int dgs_resize_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t C,
                   const int32_t* bounds_h, const int32_t* kk_v, const int32_t* bounds_v, uint8_t* out_u8, float* out_f32,
                   uint64_t f32_image_stride, dgs_stream_t stream);
 
+/* dgs_resize_rgba_u8: Pillow's Image.resize (BICUBIC) of G RGBA images in one launch (additions to ABI 15).  in u8
+ * [G,H,W,4], any alignment; the tables and the outputs as dgs_resize_u8's with C = 4: out_u8 u8 [G,h,w,4], out_f32 float
+ * planar [4,h,w] per image at f32_image_stride floats (>= 4 h w).  Pillow does not resample four independent channels: it
+ * converts to premultiplied alpha (per colour byte t = c a + 128, ((t >> 8) + t) >> 8), resamples the four bytes as
+ * dgs_resize_u8 does, and converts back (the colour copied where the resampled alpha is 0 or 255, min(255, 255 c / a)
+ * elsewhere).  When neither size changes the call is a copy / conversion WITHOUT that round trip, as Pillow's is (the colour
+ * under alpha 0 survives).  The same kernel template as dgs_resize_u8 with a fourth channel (the result tile is 4 KiB of LDS
+ * instead of 3).  Refusals as dgs_resize_u8's (no C), each with its own message. */
+int dgs_resize_rgba_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t h, int32_t w, const int32_t* kk_h,
+                       const int32_t* bounds_h, const int32_t* kk_v, const int32_t* bounds_v, uint8_t* out_u8, float* out_f32,
+                       uint64_t f32_image_stride, dgs_stream_t stream);
+
+/* dgs_rgba_over_u8: the composite of the reference's Blender reader (scene/dataset_readers.py:335-341) of G RGBA images
+ * over a black (white = 0) or white background in one launch.  in u8 [G,H,W,4], any alignment.  Per colour byte
+ *     (uint8)(int)(((c / 255.0) * (a / 255.0) + bg * (1.0 - a / 255.0)) * 255.0)
+ * in IEEE double, one rounding per operation, in this order (bg = 0.0 or 1.0, its product kept): numpy's float64 expression
+ * and its cast to np.byte, i.e. truncation.  It differs from the exact integer floor in 154 (black) / 152 (white) of the
+ * 65 536 (c, a) pairs and from a float32 evaluation in 154 / 391.  Outputs, either may be NULL but not both: out_u8 u8
+ * [G,H,W,3] (any alignment) and out_f32 float planar [3,H,W] per image, image g at out_f32 + g f32_image_stride floats
+ * (>= 3 H W), value (float)byte / 255.0f.  No temporary, nothing kept between calls, no atomics: capturable.  Refused before
+ * anything is enqueued: a NULL input, both outputs NULL, G below 1, a size outside 1..65536, an out_f32 that is not 4-byte
+ * aligned, a float image stride below 3 H W, more than 2^31 - 1 blocks. */
+int dgs_rgba_over_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t white, uint8_t* out_u8, float* out_f32,
+                     uint64_t f32_image_stride, dgs_stream_t stream);
+
 /* dgs_depth_bound_keys: the per-(camera, point) part of get_bds in double.  points double [n,3], w2c double [m,3,4] (rows
  * of the world-to-camera matrix [R | t]), both on the device; w, h, fx, fy: the FIRST camera's, used for every camera as the
  * reference does.  With cam = R p + t: u = cam.x / fx, v = cam.y / fy, d = cam.z - cam.x (w / 2) / fx - cam.y (h / 2) / fy,
