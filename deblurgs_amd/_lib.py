@@ -109,6 +109,7 @@ class DgsLpipsSqueezeWeights(ctypes.Structure):
 
 
 ADAM_MAX_GROUPS = 16
+PNG_SEGMENT = 16384        # DGS_PNG_SEGMENT of include/dgs_hip.h (tests/test_png_host.py keeps the two in step)
 ABI_VERSION = 15           # DGS_ABI_VERSION of include/dgs_hip.h (tests/test_abi.py keeps the two in step)
 
 # every symbol include/dgs_hip.h declares (tests check that the library exports exactly these)
@@ -267,6 +268,10 @@ EXPORTS = {
                          [ctypes.c_uint64, ctypes.c_void_p]),
     "dgs_depth_bound_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32] +
                              [ctypes.c_double] * 4 + [ctypes.c_void_p] * 3),
+    "dgs_png_bound": (ctypes.c_size_t, [ctypes.c_int32] * 3),
+    "dgs_png_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
+    "dgs_png_encode": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_size_t, ctypes.c_void_p,
+                                      ctypes.c_size_t] + [ctypes.c_void_p] * 3),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

@@ -44,6 +44,8 @@ SOURCES = {
     "register.hip": [],
     # the resample coefficient tables restate Pillow's double arithmetic, the depth keys numpy's, one rounding per statement
     "scene.hip": ["-ffp-contract=off"],
+    # PNG row filters, deflate and checksums: integers only
+    "png.hip": [],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

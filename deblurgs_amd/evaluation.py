@@ -591,11 +591,11 @@ def initialize_test_pose(motion, cloud, test_images, bg, tone_mapping=None, **kw
     return registration.seed_test_poses(motion, cloud, test_images, bg, tone_mapping, **kw).cameras
 
 
-def _write_view(vis_dir, i, image, gt, writer):
+def _write_view(vis_dir, i, image, gt, writer, device_png=False):
     """The three files of view i (test.py:122-126) from the image the metrics were taken of."""
     if vis_dir is not None:
         from . import report
-        report.write_view_report(vis_dir, i, image, gt.contiguous(), writer)
+        report.write_view_report(vis_dir, i, image, gt.contiguous(), writer, device_png=device_png)
 
 
 @torch.no_grad()
@@ -609,7 +609,8 @@ def _lpips_values(images, gts, weights):
 
 
 @torch.no_grad()
-def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir=None, writer=None, lpips=None):
+def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir=None, writer=None, lpips=None,
+                      device_png=False):
     """evaluate() with the cameras rendered views_per_call at a time: one K-fused forward-only call per group
     (render_path.render_group), then the per-view metrics of evaluate() on slot k, summed in the same order (LPIPS: the G
     views of a call as n_pairs = G)."""
@@ -624,7 +625,7 @@ def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, 
         for k in range(e - b):
             image = tone_mapping(images[k]).contiguous()
             gt = gt_images[b + k].to(image)
-            _write_view(vis_dir, b + k, image, gt, writer)
+            _write_view(vis_dir, b + k, image, gt, writer, device_png)
             if image.device.type == "cuda":
                 both = metrics.psnr_ssim(image, gt.contiguous())
                 psnr_test += both[2:5].reshape(3, 1).mean().item()
@@ -638,7 +639,8 @@ def _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, 
 
 
 @torch.no_grad()
-def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_dir=None, writer=None, lpips=None):
+def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_dir=None, writer=None, lpips=None,
+             device_png=False):
     """test.py:93-129: (mean PSNR, mean SSIM) over the cameras -- and, with lpips = an lpips.LPIPSWeights (on the images'
     device), (mean PSNR, mean SSIM, mean LPIPS-alex): test.py:120 on the same tone-mapped, unclamped image, one
     dgs_lpips_alex call per view (per group of views under views_per_call), its value independent of views_per_call.
@@ -650,22 +652,27 @@ def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_
     vis_dir: a directory (removed and recreated, as test.py:104-107 prepares model_path/vis_dir) that receives
     III_gt.png, III_render.png and III_error.png -- the jet-coloured L1 map -- per view (report.write_view_report: the
     images are made on the device, needs a HIP device); writer(path, array) takes the place of the files (then no
-    directory is touched).  The two floats, and the files, do not depend on views_per_call; the floats not on vis_dir."""
+    directory is touched).  The two floats, and the files, do not depend on views_per_call; the floats not on vis_dir.
+    device_png=True: the three files of a view are compressed on the device in one png.encode call instead of by PIL on
+    the host (same names, same pixels; not together with a writer)."""
     if tone_mapping is None or isinstance(tone_mapping, str):
         tone_mapping = losses.ToneMapping(tone_mapping or "identity")
     if writer is not None and vis_dir is None:
         raise ValueError("writer takes the place of the files under vis_dir: give vis_dir too (it names the paths)")
+    if device_png and writer is not None:
+        raise ValueError("device_png writes the files itself: it cannot be combined with a writer")
     if vis_dir is not None and writer is None:
         from . import report
         report.fresh_directory(vis_dir)
     if views_per_call is not None:
-        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir, writer, lpips)
+        return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir, writer, lpips,
+                                 device_png)
     psnr_test, ssim_test, lpips_test = 0.0, 0.0, 0.0
     n = len(cams)
     for i, (cam, gt) in enumerate(zip(cams, gt_images)):
         image = tone_mapping(gaussian_renderer.render(cam, cloud, bg)["render"]).contiguous()
         gt = gt.to(image)
-        _write_view(vis_dir, i, image, gt, writer)
+        _write_view(vis_dir, i, image, gt, writer, device_png)
         if image.device.type == "cuda":       # one launch for both: the values metrics.psnr / metrics.ssim return
             both = metrics.psnr_ssim(image, gt.contiguous())
             psnr_test += both[2:5].reshape(3, 1).mean().item()

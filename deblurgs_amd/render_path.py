@@ -10,6 +10,8 @@ after every training) on the batched forward-only rasteriser, with the 8-bit fra
     write_frames      PNG files through PIL when it is importable, else one .npy; encoding a video is the caller's
                       (imageio is no dependency of this package): render_spiral / render_trainview take a
                       writer(frames, path, fps) callable.
+    write_frames_png  render_frames' loop with the PNG files made on the device (deblurgs_amd/png.py): the finished bytes
+                      cross to the host, not the raw frames.  Opt-in; needs no PIL.
 
 Path geometry is the reference's, in float64 numpy: mean_camera_pose / c2w_from_eye (utils/mvg_utils.py:56-98),
 cam_to_c2w / c2w_to_cam (scene/cameras.py:77-120), center_crop_window (center_crop_with_ratio's int() arithmetic), all
@@ -393,6 +395,70 @@ def render_trainview(motion, cloud, bg, tone_mapping=None, gt_images=None, start
                              (both, "render_trainview_all.mp4")):
             writer(frames, os.path.join(directory or ".", name), fps)
     return imgs, gts, both
+
+
+@torch.no_grad()
+def write_frames_png(cams, cloud, bg, directory, tone_mapping=None, crop_ratio=1.0, frames_per_call=None):
+    """render_frames' loop with the files made on the device: per group of cameras frames_finish -> png.encode, and what
+    crosses to the host is sizes[i] bytes of finished file per frame, through two pinned buffers, written as
+    directory/00000.png ... (the names write_frames gives).  Three stages overlap: while group g is rendered and encoded,
+    the bytes of group g - 1 are copied (its sizes are read first: that many bytes are copied, not the slot) and the files
+    of group g - 2 are written.  The pixels are render_frames'; returns the paths."""
+    from . import png
+    cams = list(cams)
+    if not cams:
+        raise ValueError("no cameras")
+    groups = frame_groups(cams, FRAMES_PER_CALL if frames_per_call is None else frames_per_call)
+    H, W = int(cams[0].image_height), int(cams[0].image_width)
+    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
+        raise ValueError("write_frames_png: the cameras must share one image size")
+    window = center_crop_window(H, W, crop_ratio)
+    h, w = window[1] - window[0], window[3] - window[2]
+    if h < 1 or w < 1:
+        raise ValueError(f"crop_ratio {crop_ratio} leaves no pixel of a {W} x {H} image")
+    if cams[0].world_view_transform.device.type != "cuda":
+        raise RuntimeError("write_frames_png needs cameras and a cloud on a HIP device (no CPU fallback)")
+    os.makedirs(directory, exist_ok=True)
+    G = max(e - b for b, e in groups)
+    stride = (png.bound(w, h, 3) + 15) // 16 * 16
+    pinned = [torch.empty((G, stride), dtype=torch.uint8).pin_memory() for _ in range(2)]
+    pinned_sizes = [torch.empty(G, dtype=torch.int64).pin_memory() for _ in range(2)]
+    paths = []
+
+    def copy_bytes(job):        # stage 2: the sizes are on the host; enqueue a copy of that many bytes per file
+        job["sized"].synchronize()
+        job["sizes"] = pinned_sizes[job["slot"]][:job["count"]].tolist()
+        for k, size in enumerate(job["sizes"]):
+            pinned[job["slot"]][k, :size].copy_(job["files"][k, :size], non_blocking=True)
+        job["copied"] = torch.cuda.Event()
+        job["copied"].record()
+
+    def write(job):             # stage 3
+        job["copied"].synchronize()
+        for k, size in enumerate(job["sizes"]):
+            paths.append(os.path.join(directory, f"{job['begin'] + k:05d}.png"))
+            with open(paths[-1], "wb") as f:
+                f.write(pinned[job["slot"]][k, :size].numpy().tobytes())
+
+    jobs = []
+    for g, (b, e) in enumerate(groups):
+        files, sizes = png.encode(frames_finish(render_group(cams[b:e], cloud, bg)["render"], tone_mapping, window))
+        job = {"slot": g % 2, "begin": b, "count": e - b, "files": files, "sized": torch.cuda.Event()}
+        pinned_sizes[job["slot"]][:e - b].copy_(sizes.view(torch.int64), non_blocking=True)
+        job["sized"].record()
+        jobs.append(job)
+        if g >= 2:
+            write(jobs[g - 2])
+            jobs[g - 2] = None
+        if g >= 1:
+            copy_bytes(jobs[g - 1])
+    for job in jobs[-2:]:
+        if job is not None and "copied" not in job:
+            copy_bytes(job)
+    for job in jobs[-2:]:
+        if job is not None:
+            write(job)
+    return paths
 
 
 def write_frames(frames, directory):

@@ -18,7 +18,8 @@ images never leave the device until they are bytes:
 
 The jet table is built from the published segment definition (render_path._JET_SEGMENTS; matplotlib need not be
 installed) and pinned by tests/golden/report_golden.npz.  PNG files are written through PIL when it is importable, else
-.npy; every writer argument is a callable writer(path, array) that takes the place of the file.
+.npy; every writer argument is a callable writer(path, array) that takes the place of the file.  device_png=True
+(write_view_report, traj_render, evaluation.evaluate) compresses the files on the device instead (deblurgs_amd/png.py).
 
 Out of scope: colorize with a mask or a colour bar (cv2, a matplotlib canvas), camera-cone drawings, alignment plots,
 videos.  (LPIPS, the third number of evaluate(), is deblurgs_amd/lpips.py: evaluate(..., lpips=weights).)
@@ -237,11 +238,27 @@ def evaluate_names(i):
     return f"{i:03d}_gt.png", f"{i:03d}_render.png", f"{i:03d}_error.png"
 
 
-def write_view_report(directory, i, image, gt, writer=None):
+def _no_writer_with_device_png(writer, device_png):
+    if device_png and writer is not None:
+        raise ValueError("device_png writes the files itself: it cannot be combined with a writer")
+
+
+def write_device_png(directory, names, images_u8):
+    """images_u8 uint8 [n,H,W,3] on the device -> the n files directory/names[k], compressed on the device in ONE
+    png.encode call (the host reads the sizes and copies that many bytes).  Returns the paths."""
+    from . import png
+    return png.write_files(images_u8, [os.path.join(directory, name) for name in names])
+
+
+def write_view_report(directory, i, image, gt, writer=None, device_png=False):
     """The three files of test view i (test.py:122-126) from ONE view_report call: image [3,H,W] is the tone-mapped,
     unclamped render the metrics were taken of (so the bytes and the error are those of the reference's torch
-    expression, no second tone mapping), gt [3,H,W]."""
+    expression, no second tone mapping), gt [3,H,W].  device_png=True: the three images become files on the device (one
+    n = 3 png.encode call) instead of crossing to PIL; same names, same pixels."""
+    _no_writer_with_device_png(writer, device_png)
     render_u8, gt_u8, error_u8 = view_report(image[None], gt[None], "identity")
+    if device_png:
+        return write_device_png(directory, evaluate_names(i), torch.stack([gt_u8[0], render_u8[0], error_u8[0]]))
     host = torch.stack([gt_u8[0], render_u8[0], error_u8[0]]).cpu().numpy()
     return [write_image(os.path.join(directory, name), host[k], writer) for k, name in enumerate(evaluate_names(i))]
 
@@ -258,7 +275,7 @@ def traj_render_names(i, num_visualize_subframes):
 
 @torch.no_grad()
 def traj_render(motion, cloud, model_path, iteration, tone_mapping=None, num_visualize_subframes=3, background=None,
-                writer=None, *, _two_calls=None):
+                writer=None, *, device_png=False, _two_calls=None):
     """Visualizer.traj_render (utils/visualization.py:262-291): for every training view of `motion` the files
     III_00.png ... (num_visualize_subframes evenly spaced sharp subframes), III_blur.png, III_gt.png and III_l1.png (the jet
     L1 error map of the blurred synthesis) under {model_path}/traj_render_{iteration:05d}, which is removed and recreated
@@ -269,7 +286,9 @@ def traj_render(motion, cloud, model_path, iteration, tone_mapping=None, num_vis
     same call, finished with mean=0.  That is what the reference's two query() calls render while
     motion.curve_random_sample is off (both see the same trajectory); with it on two calls are made
     as the reference makes them, each with its own draw.  One background is drawn per view (background None: torch.rand(3))
-    and used for both; the reference draws one per query()."""
+    and used for both; the reference draws one per query().  device_png=True: the n + 3 images of a view are compressed
+    on the device in one png.encode call instead of by PIL on the host (same names, same pixels; not with a writer)."""
+    _no_writer_with_device_png(writer, device_png)
     device = cloud._xyz.device
     if device.type != "cuda":
         raise RuntimeError("traj_render needs a motion module and a cloud on a HIP device (no CPU fallback)")
@@ -295,6 +314,9 @@ def traj_render(motion, cloud, model_path, iteration, tone_mapping=None, num_vis
         blur_u8, gt_u8, err = report_images(all_frames, tone_mapping, mean=True, gt=motion.get_gt_image(i))
         sub_u8, _, _ = report_images(shown, tone_mapping, mean=False)
         l1_u8 = colorize(err[0])
+        if device_png:
+            paths += write_device_png(directory, traj_render_names(i, n_sub), torch.cat([sub_u8, blur_u8, gt_u8, l1_u8[None]]))
+            continue
         host = torch.cat([sub_u8, blur_u8, gt_u8, l1_u8[None]]).cpu().numpy()
         for k, name in enumerate(traj_render_names(i, n_sub)):
             paths.append(write_image(os.path.join(directory, name), host[k], writer))

@@ -912,6 +912,38 @@ int dgs_rgba_over_u8(const uint8_t* in, int32_t G, int32_t H, int32_t W, int32_t
 int dgs_depth_bound_keys(const double* points, int32_t n, const double* w2c, int32_t m, double w, double h, double fx,
                          double fy, float* keys, uint32_t* counts, dgs_stream_t stream);
 
+/* ---- PNG files made on the device (additions to ABI 15) ----
+ * dgs_png_encode: n 8-bit images -> n finished .png files, every byte made on the device: signature, IHDR, ONE IDAT holding
+ * a zlib stream, IEND and every CRC.  channels 1 / 2 / 3 / 4 is colour type 0 / 4 / 2 / 6 (gray, gray + alpha, RGB, RGBA), bit
+ * depth 8, no interlace, no ancillary chunk.  Image i is h w channels contiguous bytes at images + i image_stride, any
+ * alignment; file i starts at files + i file_stride (file_stride >= dgs_png_bound, any alignment) and sizes[i] (a device
+ * uint64, 8-byte aligned) is its length; the bytes of the slot past sizes[i] are not written.  The host reads a size, copies
+ * that many bytes and writes them.
+ *   row filter   per row the candidate (None, Sub, Up, Average, Paeth; bpp = channels; the row above row 0 is zeros) with the
+ *                smallest sum of |residual as int8| over the row, the lowest filter type on a tie.  The filtered stream is
+ *                F = h (1 + w channels) bytes.
+ *   deflate      the filtered stream is cut into segments of DGS_PNG_SEGMENT bytes, each compressed on its own (no reference
+ *                to an earlier byte) with zlib's Z_RLE tokens -- a literal, then matches of distance 1 and length 3..258
+ *                while the byte repeats, a tail shorter than 3 as literals -- and dynamic Huffman codes (BTYPE 10) built from
+ *                the SEGMENT's own histogram: literal/length lengths limited to 15 bits, the code-length code to 7, both
+ *                complete; one distance code of length 1.  A segment whose compressed form, marker included, is not smaller
+ *                than 5 + len is a stored block.  A non-final compressed segment is followed by an empty stored block, so
+ *                the next starts on a byte; the last block carries BFINAL.
+ *   checksums    Adler-32 from per-segment (sum, weighted sum) pairs, each chunk's CRC-32 from per-segment remainders
+ *                shifted by x^(8 bytes after it) mod the polynomial (the published combine rule).
+ * Four launches on the caller's stream, integers only, every sum an integer sum or an OR: the bytes are a function of the
+ * arguments.  tmp: dgs_png_tmp_bytes(n, w, h, channels) bytes of the caller's, any alignment; nothing is allocated, no host
+ * synchronisation, nothing kept between calls: capturable.  dgs_png_bound = 63 + F + 5 ceil(F / DGS_PNG_SEGMENT): 8 signature
+ * + 25 IHDR + 12 IDAT framing + 2 zlib header + 4 Adler + 12 IEND, and the stored-block fallback of every segment; 0 for
+ * arguments the call refuses.  n = 0 succeeds without a launch.  Refused before anything is enqueued: channels outside 1..4,
+ * w or h below 1, F >= 2^31, a negative n, a NULL pointer, an image_stride below h w channels, a file_stride below the bound,
+ * a misaligned sizes, more than 2^31 - 1 blocks. */
+#define DGS_PNG_SEGMENT 16384
+size_t dgs_png_bound(int32_t w, int32_t h, int32_t channels);
+size_t dgs_png_tmp_bytes(int32_t n, int32_t w, int32_t h, int32_t channels);
+int dgs_png_encode(const uint8_t* images, int32_t n, int32_t w, int32_t h, int32_t channels, size_t image_stride,
+                   uint8_t* files, size_t file_stride, uint64_t* sizes, void* tmp, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
