@@ -55,7 +55,12 @@ def quat_to_rotmat(q):
 
 def preprocess(means3D, opacities, viewmatrix, projmatrix, campos, W, H, tanfovx, tanfovy, sh=None,
                colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=0,
-               scale_modifier=1.0, use_sigmoid=False, pix_offset=None):
+               scale_modifier=1.0, use_sigmoid=False, pix_offset=None, reference_clamp=False):
+    """reference_clamp (default off: every gradient is autograd's own): differentiate the guard-band clamp of t.x, t.y
+    the way the reference's backward does.  backward.cu computeCov2DCUDA takes dL/dJ02 of J02 = -focal_x t.x / t.z^2
+    with the CLAMPED t.x held fixed (no d t.x / d t.z term) and multiplies dL/dt.x by x_grad_mul = 0, so a clamped t.x
+    is a constant there, while autograd sees clamp(x / z) * z move with z.  On: a clamped t.x is that value detached, an
+    unclamped one is p_view.x itself; likewise t.y.  Forward values do not change."""
     dt = means3D.dtype
     P = means3D.shape[0]
     V = viewmatrix.reshape(4, 4)   # row-vector convention: p_view = [p,1] @ V
@@ -82,6 +87,10 @@ def preprocess(means3D, opacities, viewmatrix, projmatrix, campos, W, H, tanfovx
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
     tx = torch.clamp(p_view[:, 0] / tz, -limx, limx) * tz
     ty = torch.clamp(p_view[:, 1] / tz, -limy, limy) * tz
+    if reference_clamp:
+        rx, ry = (p_view[:, 0] / tz).detach(), (p_view[:, 1] / tz).detach()
+        tx = torch.where((rx < -limx) | (rx > limx), tx.detach(), p_view[:, 0])
+        ty = torch.where((ry < -limy) | (ry > limy), ty.detach(), p_view[:, 1])
     zero = torch.zeros_like(tz)
     Jm = torch.stack([focal_x / tz, zero, -(focal_x * tx) / (tz * tz),
                       zero, focal_y / tz, -(focal_y * ty) / (tz * tz)], 1).reshape(P, 2, 3)

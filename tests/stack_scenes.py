@@ -222,10 +222,10 @@ def checker_kw(name):
     return dict(ill_frac=0, ill_min=0, well_frac=1.0) if flat_bars(name) else {}
 
 
-def float64_reference(sc, k, gC, gD):
+def float64_reference(sc, k, gC, gD, **kw):
     """Subframe k through the dense torch rasteriser (oracle/torch_naive.py) in float64 and autograd: the image, the radii
     and the gradients F64_KEYS of <colour, gC> + <depth, gD>.  The two analytic columns of dL_dprojmatrix are given in the
-    reference's units (backward.cu:430-450: times 0.5 W / 0.5 H)."""
+    reference's units (backward.cu:430-450: times 0.5 W / 0.5 H).  kw: further keywords of torch_naive.rasterize."""
     import torch
     from oracle import torch_naive
     T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
@@ -233,7 +233,7 @@ def float64_reference(sc, k, gC, gD):
     V, F = T(sc["viewmatrix"][k]).requires_grad_(True), T(sc["projmatrix"][k]).requires_grad_(True)
     c, d, r = torch_naive.rasterize(inp["means3D"], inp["opacities"], V, F, T(sc["campos"][k]), T(sc["bg"]), sc["W"],
                                     sc["H"], sc["tanfovx"], sc["tanfovy"], sh=inp["sh"], scales=inp["scales"],
-                                    rotations=inp["rotations"], sh_degree=sc["sh_degree"])
+                                    rotations=inp["rotations"], sh_degree=sc["sh_degree"], **kw)
     loss = (c * T(gC)).sum()
     if gD is not None:
         loss = loss + (d * T(gD)).sum()

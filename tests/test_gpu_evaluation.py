@@ -387,15 +387,18 @@ class _NoHostSync:
         return False
 
 
-def _fit_fixture(P=3000, W=144, H=96, seed=3):
+def _fit_fixture(P=3000, W=144, H=96, seed=3, move=None):
     """A product cloud, three test views whose ground truth is the product's own render (gamma tone mapping) at known
-    poses, and start poses off by a fixed rotation (0.4 degrees about a fixed axis) and translation."""
+    poses, and start poses off by a fixed rotation (0.4 degrees about a fixed axis) and translation.  move: a map from
+    the scene to the scene the fixture is built on (tests/test_gpu_posed.py: the same cloud and views at a general pose)."""
     import torch
     from scipy.spatial.transform import Rotation
     from deblurgs_amd import evaluation as ev, gaussian_renderer, losses
     from deblurgs_amd.cloud import GaussianCloud
     torch.manual_seed(seed)
     sc = synthetic.make_scene(P, W, H, K=3, seed=seed, sigma_px=2.5)
+    if move is not None:
+        sc = move(sc)
     cloud = GaussianCloud.from_scene(sc, "cuda")
     tm = losses.ToneMapping("gamma")
     bg = torch.tensor([0.2, 0.3, 0.1], device="cuda")
@@ -425,11 +428,16 @@ def _pose_error(model, truth, cloud):
 
 def test_fused_pose_fit_first_step_gradients_match_autograd(gpu):
     """dL/dq and dL/dt of the fused path against render() + losses + torch.autograd + the torch pose chain."""
+    _check_first_step_gradients(_fit_fixture())
+
+
+def _check_first_step_gradients(fixture):
     import torch
     from deblurgs_amd import evaluation as ev, gaussian_renderer
-    cloud, start, gts, bg, tm, _ = _fit_fixture()
+    cloud, start, gts, bg, tm, _ = fixture
     fit = ev.FusedPoseFit(cloud, start, gts, bg, tm, num_iter_per_view=60)
     ref = ev.TestPoseModel(start, device="cuda")
+    errs = []
     for idx in range(3):
         g_rot, g_trans, vals = fit.gradients(idx)
         for p in ref.parameters():
@@ -441,9 +449,11 @@ def test_fused_pose_fit_first_step_gradients_match_autograd(gpu):
         for name, a, b in (("dL/dq", g_rot, ref._rot.grad), ("dL/dt", g_trans, ref._trans.grad)):
             e = relerr(a.cpu().numpy(), b.cpu().numpy())
             print(f"view {idx} {name}: rel err {e:.3e}")
+            errs.append(e)
             assert e <= GRAD_TOL, (idx, name, e)
             assert float(a[[i for i in range(3) if i != idx]].abs().max()) == 0.0      # the dense gradient's other rows
         assert abs(float(vals[0]) - float(l1)) <= 1e-6 and abs(float(vals[1]) - float(mse)) <= 1e-6
+    return errs
 
 
 def test_fused_pose_fit_against_the_autograd_fit(gpu):

@@ -238,7 +238,10 @@ def test_depth_order_beyond_27_key_bits_through_the_forward(gpu):
 
 
 def test_forward_images(scene_states):
-    sc, hip, ora = scene_states
+    _check_forward_images(*scene_states)
+
+
+def _check_forward_images(sc, hip, ora):
     ex = exempt_pixels(sc, sc["K"], ora)
     for k, o in enumerate(ora):
         unstable = ex[k]                      # where the two traversals took a different per-pair decision
