@@ -6,8 +6,10 @@ of ``bench.py`` -- never by the product package ``deblurgs_amd``.
 One call = one subframe, with the reference's semantics
 (/root/reference/submodules/diff-gaussian-rasterization/cuda_rasterizer/rasterizer_impl.cu:198-463).
 Every intermediate of the reference's Geometry/Binning/Image state is returned so the HIP kernels can be
-checked stage by stage.  Parity status: see the header of dgs_oracle.cpp ("parity unpinned" for the L0
-kernels; pinned pieces listed there).
+checked stage by stage.  Parity status: pinned to the reference's own kernels, compiled for gfx950 by
+oracle/ref_rasterizer.py and run on the device by tests/test_gpu_reference_kernels.py (geometry state, keys, lists
+and ranges bitwise equal; images and gradients within the parity tests' bars): see the header of dgs_oracle.cpp
+and DESIGN section 5.
 """
 import ctypes
 import os

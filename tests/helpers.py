@@ -300,7 +300,7 @@ def _hip_forward_state(scene, K, sh_degree, use_sigmoid, colors_precomp, cov3D_p
 
 
 def hip_forward_backward(scene, K, dL_dcolor, dL_ddepth=None, sh_degree=None, use_sigmoid=False, fused=True,
-                         colors_precomp=None, cov3D_precomp=None):
+                         colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0):
     """Forward + backward through the public operator (autograd).  fused=False uses the K=1 reference API K
     times (and sums per-Gaussian grads like autograd does in the reference loop)."""
     import torch
@@ -320,7 +320,7 @@ def hip_forward_backward(scene, K, dL_dcolor, dL_ddepth=None, sh_degree=None, us
               scales=inp["scales"] if cov is None else None, rotations=inp["rotations"] if cov is None else None,
               cov3D_precomp=cov)
     if fused:
-        rs = hip_settings(scene, K, sh_degree, use_sigmoid)._replace(campos=_t(scene["campos"][:K]))
+        rs = hip_settings(scene, K, sh_degree, use_sigmoid, scale_modifier)._replace(campos=_t(scene["campos"][:K]))
         m2 = torch.zeros((K, P, 3), device=dev, requires_grad=True)
         color, depth, radii = GaussianRasterizer(rs).forward_subframes(
             inp["means3D"], m2, inp["opacities"], viewmatrices=view, projmatrices=proj, **kw)
@@ -338,7 +338,7 @@ def hip_forward_backward(scene, K, dL_dcolor, dL_ddepth=None, sh_degree=None, us
         colors, depths, radiis, m2s = [], [], [], []
         loss = 0
         for k in range(K):
-            rs = hip_settings(scene, 1, sh_degree, use_sigmoid, campos=scene["campos"][k:k + 1])
+            rs = hip_settings(scene, 1, sh_degree, use_sigmoid, scale_modifier, campos=scene["campos"][k:k + 1])
             m2 = torch.zeros((P, 3), device=dev, requires_grad=True)
             c, d, r = GaussianRasterizer(rs)(inp["means3D"], m2, inp["opacities"], viewmatrix=view[k],
                                              projmatrix=proj[k], **kw)

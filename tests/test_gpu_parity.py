@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import ref_checks
 from helpers import (OracleRun, assert_grads_close, exempt_pixels, tile_cull, wide_records, hip_forward_backward, hip_forward_state,
                      oracle_forward, oracle_forward_backward, relerr, synthetic, unstable_pixels)
 
@@ -153,24 +154,11 @@ def test_preprocess_bit_exact(scene_states):
 
 
 def _check_preprocess_bits(sc, hip, ora, min_visible=100, relu=True):
-    for k, o in enumerate(ora):
+    """The product's packed rows against the oracle, through the layout-neutral checker (ref_checks.check_preprocess)."""
+    ref_checks.check_preprocess(ref_checks.plain_geometry(hip), ora, min_visible=min_visible, relu=relu)
+    for k, o in enumerate(ora):          # the radius rides in the row's last word as well
         vis = o["radii"] > 0
-        assert vis.sum() > min_visible
-        assert np.array_equal(hip["radii"][k], o["radii"]), "radii"
-        assert np.array_equal(hip["tiles_touched"][k], o["tiles_touched"]), "tiles_touched"
-        rows = hip["rows"][k][vis]
-        # pixel-space means, conic, opacity, depth: same IEEE op order, no FMA contraction -> identical bits
-        assert np.array_equal(rows[:, 0:2].view(np.uint32), o["means2D"][vis].view(np.uint32)), "means2D bits"
-        assert np.array_equal(rows[:, 9].view(np.uint32), o["depths"][vis].view(np.uint32)), "depth bits"
-        assert np.array_equal(rows[:, 2:6].view(np.uint32), o["conic_opacity"][vis].view(np.uint32)), "conic bits"
-        assert np.abs(rows[:, 6:9] - o["rgb"][vis]).max() <= 1e-6, "rgb"
         assert np.array_equal(hip["rows_u32"][k][vis][:, 11].view(np.int32), o["radii"][vis])
-        if relu:
-            assert np.array_equal(hip["pre_sigmoid"][k][vis], o["pre_sigmoid"][vis]), "relu mask"
-        else:   # sigmoid activation: the pre-activation colours, an SH sum like rgb
-            assert np.abs(hip["pre_sigmoid"][k][vis] - o["pre_sigmoid"][vis]).max() <= 1e-5, "pre-sigmoid colours"
-    wrote = np.any(ora[0]["cov3D"] != 0, axis=1)     # the oracle fills cov3D only past the near-plane cull
-    assert np.array_equal(hip["cov3D"][wrote].view(np.uint32), ora[0]["cov3D"][wrote].view(np.uint32)), "cov3D bits"
 
 
 def test_binning_bit_exact(scene_states):
@@ -192,19 +180,8 @@ def _check_binning_bits(sc, hip, ora):
     vis_flat = flat_tt > 0
     # (the first-duplicate offset of every visible pair lives in the K*P-word side array, by natural index)
     assert np.array_equal(hip["point_offsets"].reshape(-1)[vis_flat], offs[vis_flat].astype(np.uint32))
-    off = 0
-    for k, o in enumerate(ora):
-        R = Rs[k]
-        keys = hip["keys"][off:off + R]
-        # reference key = (tile << 32) | depth_bits; the fused key carries k*T on top of the tile id
-        assert np.array_equal(keys - (np.uint64(k * T) << np.uint64(32)), o["keys"]), "sort keys"
-        assert np.array_equal(hip["point_list"][off:off + R], o["point_list"]), "point_list"
-        rng = hip["ranges"][k].astype(np.int64)
-        ref = o["ranges"].astype(np.int64)
-        nonempty = ref[:, 1] > ref[:, 0]
-        assert np.array_equal(rng[nonempty] - off, ref[nonempty]), "tile ranges"
-        assert np.all(rng[~nonempty, 1] - rng[~nonempty, 0] == 0)
-        off += R
+    # reference key = (tile << 32) | depth_bits; the fused key carries k*T on top of the tile id (ref_checks.plain_binning)
+    ref_checks.check_binning(ref_checks.plain_binning(hip, Rs), ora)
     assert hip["sort_bits"] == 32 + __import__("oracle.oracle", fromlist=["x"]).higher_msb(T * sc["K"])
 
 
@@ -242,18 +219,11 @@ def test_forward_images(scene_states):
 
 
 def _check_forward_images(sc, hip, ora):
-    ex = exempt_pixels(sc, sc["K"], ora)
+    ex = exempt_pixels(sc, sc["K"], ora)      # where the two traversals took a different per-pair decision
     for k, o in enumerate(ora):
-        unstable = ex[k]                      # where the two traversals took a different per-pair decision
+        unstable = ex[k]
         assert unstable.mean() < 2e-4 and unstable.sum() <= unstable_pixels(o).sum() + 2
-        dc = np.abs(hip["color"][k] - o["color"]).max(axis=0)
-        dd = np.abs(hip["depth"][k][0] - o["depth"][0]) / sc["z_far"]
-        assert dc[~unstable].max() <= IMG_TOL, f"colour k={k}: {dc[~unstable].max()}"
-        assert dd[~unstable].max() <= DEPTH_TOL, f"depth k={k}: {dd[~unstable].max()}"
-        assert dc.max() <= 2e-2 and dd.max() <= 2e-2       # a flipped threshold moves one pair's weight only
-        s = ~unstable.reshape(-1)
-        assert np.array_equal(hip["n_contrib"][k][s], o["n_contrib"][s]), "n_contrib"
-        assert np.abs(hip["final_T"][k][s] - o["final_T"][s]).max() <= 1e-5, "final_T"
+    ref_checks.check_images(ref_checks.plain_images(hip), ora, ex, sc["z_far"])
 
 
 def _grads(sc, K, seed=5, depth=True, **kw):
@@ -1190,14 +1160,12 @@ FUZZ = [
 FUZZ = FUZZ + _fuzz_sweep(int(os.environ.get("DGS_FUZZ_SWEEP", "0")))
 
 
-@pytest.mark.parametrize("P,W,H,K,seed,sigma,deg,kw", FUZZ)
-def test_fuzz_shapes_against_oracle(gpu, P, W, H, K, seed, sigma, deg, kw):
-    sc = synthetic.make_scene(P, W, H, K=K, seed=seed, sigma_px=sigma, sh_degree=deg)
+def adversarial_sprinkles(sc, seed):
+    """Opacity extremes, near-plane crossers, degenerate scales, elongated splats, a far off-screen giant (in place).  These
+    are ill-conditioned in fp32 by themselves (the oracle deviates from float64 autograd by up to 1e-2 of the largest
+    gradient on 200:1 splats), so elongation is kept at 12:1 and the gradient bar of the fuzz test is 1e-3 instead of the
+    1e-4 of the well-conditioned scenes above."""
     rng = np.random.default_rng(seed)
-    # adversarial sprinkles: opacity extremes, near-plane crossers, degenerate scales, elongated splats, a far
-    # off-screen giant.  These are ill-conditioned in fp32 by themselves (the oracle deviates from float64 autograd
-    # by up to 1e-2 of the largest gradient on 200:1 splats), so elongation is kept at 12:1 and the gradient bar
-    # of this test is 1e-3 instead of the 1e-4 of the well-conditioned scenes above.
     sc["opacities"][:20] = 1.0
     sc["opacities"][20:40] = 0.0
     sc["opacities"][40:60] = 1.0 / 255.0
@@ -1206,6 +1174,13 @@ def test_fuzz_shapes_against_oracle(gpu, P, W, H, K, seed, sigma, deg, kw):
     sc["scales"][90:100, 0] *= 12.0
     sc["means3D"][100] = [50.0, -40.0, 2.0]
     sc["scales"][100] = 5.0
+    return sc
+
+
+@pytest.mark.parametrize("P,W,H,K,seed,sigma,deg,kw", FUZZ)
+def test_fuzz_shapes_against_oracle(gpu, P, W, H, K, seed, sigma, deg, kw):
+    sc = synthetic.make_scene(P, W, H, K=K, seed=seed, sigma_px=sigma, sh_degree=deg)
+    adversarial_sprinkles(sc, seed)
     gC, gD = _grads(sc, K, seed=seed)
     hip = hip_forward_backward(sc, K, gC, gD, **kw)
     ora = oracle_forward_backward(sc, K, gC, gD, **kw)
