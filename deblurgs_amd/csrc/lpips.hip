@@ -12,6 +12,10 @@
 //     (net_type='squeeze', networks.py:69-77);
 //   * layer_distance_kernel + lpips_finish_kernel: per tap the channel-normalised squared difference under the "lin"
 //     weights, reduced over space in block order.
+// The host side knows a backbone as a layer program -- a constant table of (operation, shape, tap, pool that follows):
+// ALEX, VGG, SQUEEZE -- and has ONE plan function (lpips_plan: every layer's sizes, the taps' table, the two ping-pong
+// buffers and the partials) and ONE driver (lpips_run: layer, layer distance where the layer is a tap, pool, ...,
+// finish) for all three; dgs_lpips_{alex,vgg,squeeze} only flatten their weight structs for it.
 // Built with -ffp-contract=off (deblurgs_amd/build.py): the compensated sum of the convolution below is only what it says
 // while the compiler forms no FMA across its statements, and (x - mean) / std and the distance's sums round once per
 // statement, as the torch expressions do.
@@ -21,6 +25,8 @@
 // So a pair's six numbers are bitwise those of a call on that pair alone, lpips(x, x) is exactly 0 and
 // lpips(x, y) == lpips(y, x) ((a - b)^2 == (b - a)^2).  No float atomics anywhere.
 #include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
 
 #include "dgs_common.h"
 
@@ -848,60 +854,7 @@ __global__ void __launch_bounds__(256) lpips_finish_kernel(const double* __restr
 }
 
 // ---- host side
-struct ConvShape {
-  int Cout, Cin, k, stride, pad, pool;
-};
-const ConvShape LP_CONVS[5] = {{64, 3, 11, 4, 2, 1}, {192, 64, 5, 1, 2, 1}, {384, 192, 3, 1, 1, 0},
-                               {256, 384, 3, 1, 1, 0}, {256, 256, 3, 1, 1, 0}};
-
-struct LpipsPlan {
-  int oh[5], ow[5];   // the taps' sizes
-  int ph[2], pw[2];   // the two pooled sizes
-  size_t buf_a, buf_b;  // floats: buf_a holds taps 1, 2, 3, 5, buf_b the two pooled maps and tap 4
-  size_t off_b, off_partials, total_bytes;
-  LpipsTaps taps;
-};
-
 size_t lp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// false: an image below 31 x 31, no pairs, or sizes this launch arithmetic does not cover
-bool lpips_plan(int W, int H, int n_pairs, LpipsPlan& P) {
-  if (W < LP_MIN || H < LP_MIN || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
-  int h = H, w = W, np = 0;
-  const size_t n_img = 2 * (size_t)n_pairs;
-  size_t a = 0, b = 0, partial = 0;
-  for (int l = 0; l < 5; l++) {
-    const ConvShape& c = LP_CONVS[l];
-    h = (h + 2 * c.pad - c.k) / c.stride + 1;
-    w = (w + 2 * c.pad - c.k) / c.stride + 1;
-    P.oh[l] = h;
-    P.ow[l] = w;
-    const size_t tap = n_img * c.Cout * (size_t)h * w;
-    if (l == 3) b = tap > b ? tap : b; else a = tap > a ? tap : a;
-    P.taps.first[l] = partial;
-    P.taps.blocks[l] = (h * w + 255) / 256;
-    P.taps.hw[l] = (double)h * (double)w;
-    partial += (size_t)n_pairs * P.taps.blocks[l];
-    if (c.pool) {
-      h = (h - 3) / 2 + 1;
-      w = (w - 3) / 2 + 1;
-      P.ph[np] = h;
-      P.pw[np] = w;
-      np++;
-      const size_t pooled = n_img * c.Cout * (size_t)h * w;
-      b = pooled > b ? pooled : b;
-    }
-  }
-  // (int32 arithmetic of the kernels: pixels of a call, elements of one image's feature map)
-  if (n_img * (size_t)P.oh[0] * P.ow[0] >= ((size_t)1 << 31) || (size_t)3 * H * W >= ((size_t)1 << 31)) return false;
-  P.taps.n = 5;
-  P.buf_a = a;
-  P.buf_b = b;
-  P.off_b = lp_align(a * sizeof(float));
-  P.off_partials = P.off_b + lp_align(b * sizeof(float));
-  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
-  return true;
-}
 
 hipError_t launch_conv(const ConvArgs& g, bool zscore, hipStream_t s) {
   const unsigned gx = (unsigned)((g.N + LP_BN - 1) / LP_BN);
@@ -920,12 +873,6 @@ hipError_t launch_conv(const ConvArgs& g, bool zscore, hipStream_t s) {
   }
   return hipGetLastError();
 }
-
-// ---- VGG16 (networks.py:88-96): thirteen 3 x 3 convolutions; taps after convolutions 2, 4, 7, 10 (each before its 2 x 2
-// pool) and 13
-constexpr int VGG_N = 13;
-const int VGG_COUT[VGG_N] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
-const int VGG_TAP[VGG_N] = {-1, 0, -1, 1, -1, -1, 2, -1, -1, 3, -1, -1, 4};
 
 // Which convolution kernel a VGG layer runs on: a function of the layer shape only (DESIGN.md 7 has the per-layer timings
 // behind it).  The halo-tile kernel won every layer but the first by 8 % and more in every round; on 3 -> 64 channels
@@ -968,47 +915,6 @@ hipError_t launch_maxpool2x2(const float* in, size_t planes, int IH, int IW, flo
   return hipGetLastError();
 }
 
-struct VggPlan {
-  int h[5], w[5];       // the taps' sizes
-  size_t off_b, off_partials, total_bytes;   // two ping-pong buffers of the largest layer output [n_img,64,H,W], the partials
-  LpipsTaps taps;
-};
-
-// false: an image below 16 x 16, no pairs, or sizes the kernels' 32-bit arithmetic does not cover
-bool vgg_plan(int W, int H, int n_pairs, VggPlan& P) {
-  if (W < V_MIN || H < V_MIN || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
-  const size_t n_img = 2 * (size_t)n_pairs;
-  // (elements of one image's largest feature map, pixels of a call)
-  if ((size_t)64 * H * W >= ((size_t)1 << 31) || n_img * (size_t)H * W >= ((size_t)1 << 31)) return false;
-  int h = H, w = W;
-  size_t partial = 0;
-  for (int t = 0; t < 5; t++) {
-    P.h[t] = h;
-    P.w[t] = w;
-    P.taps.first[t] = partial;
-    P.taps.blocks[t] = (h * w + 255) / 256;
-    P.taps.hw[t] = (double)h * (double)w;
-    partial += (size_t)n_pairs * P.taps.blocks[t];
-    h /= 2;
-    w /= 2;
-  }
-  P.taps.n = 5;
-  const size_t buf = lp_align(n_img * 64 * (size_t)H * W * sizeof(float));
-  P.off_b = buf;
-  P.off_partials = 2 * buf;
-  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
-  return true;
-}
-
-// ---- SqueezeNet 1.1 (networks.py:69-77): conv 3 x 3 / 2 (no padding), ReLU, pool, Fire 1, Fire 2, pool, Fire 3, Fire 4,
-// pool, Fire 5 .. 8; pools 3 x 3 / 2 in ceil mode; taps: the first ReLU and Fires 2, 4, 5, 6, 7, 8 (each before its pool)
-struct FireShape {
-  int Cin, S, E, tap, pool;   // tap: the tap this module's output is (-1: none); pool: pooled afterwards
-};
-const FireShape SQ_FIRES[8] = {{64, 16, 64, -1, 0},  {128, 16, 64, 1, 1},  {128, 32, 128, -1, 0}, {256, 32, 128, 2, 1},
-                               {256, 48, 192, 3, 0}, {384, 48, 192, 4, 0}, {384, 64, 256, 5, 0},  {512, 64, 256, 6, 0}};
-const int SQ_TAP_C[7] = {64, 128, 256, 384, 384, 512, 512};
-
 size_t fire_tiles(int64_t n_img, int64_t H, int64_t W) { return conv3x3_tiles(n_img, H, W); }
 
 // Grid rows (how many blocks share the expand slabs of one tile; each repeats stage 1): per pixel stage 1 is Cin S
@@ -1040,49 +946,206 @@ hipError_t launch_maxpool_ceil(const float* in, size_t planes, int IH, int IW, f
   return hipGetLastError();
 }
 
-struct SqueezePlan {
-  int h[7], w[7];       // the taps' sizes
-  int fh[8], fw[8];     // the Fire modules' map sizes
-  size_t off_b, off_partials, total_bytes;   // two ping-pong buffers of the first convolution's output, the partials
-  LpipsTaps taps;
-};
-
-// false: an image below 17 x 17, no pairs, or sizes the kernels' 32-bit arithmetic does not cover
-bool squeeze_plan(int W, int H, int n_pairs, SqueezePlan& P) {
-  if (W < Q_MIN || H < Q_MIN || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
-  const size_t n_img = 2 * (size_t)n_pairs;
-  const int h0 = (H - 3) / 2 + 1, w0 = (W - 3) / 2 + 1;
-  // (elements of one input image, of one image's largest feature map, pixels of a call)
-  if ((size_t)3 * H * W >= ((size_t)1 << 31) || (size_t)64 * h0 * w0 >= ((size_t)1 << 31) ||
-      n_img * (size_t)h0 * w0 >= ((size_t)1 << 31))
-    return false;
-  int h = h0, w = w0;
-  P.h[0] = h, P.w[0] = w;
-  h /= 2, w /= 2;
-  for (int f = 0; f < 8; f++) {
-    P.fh[f] = h, P.fw[f] = w;
-    const int t = SQ_FIRES[f].tap;
-    if (t >= 0) P.h[t] = h, P.w[t] = w;
-    if (SQ_FIRES[f].pool) h /= 2, w /= 2;
-  }
-  size_t partial = 0;
-  for (int t = 0; t < 7; t++) {
-    P.taps.first[t] = partial;
-    P.taps.blocks[t] = (P.h[t] * P.w[t] + 255) / 256;
-    P.taps.hw[t] = (double)P.h[t] * (double)P.w[t];
-    partial += (size_t)n_pairs * P.taps.blocks[t];
-  }
-  P.taps.n = 7;
-  const size_t buf = lp_align(n_img * 64 * (size_t)h0 * w0 * sizeof(float));
-  P.off_b = buf;
-  P.off_partials = 2 * buf;
-  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
-  return true;
+hipError_t launch_maxpool_floor(const float* in, size_t planes, int IH, int IW, float* out, hipStream_t s) {
+  const int PH = (IH - 3) / 2 + 1, PW = (IW - 3) / 2 + 1;
+  const size_t total = planes * PH * PW, want = (total + 255) / 256;
+  hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)(want < (1u << 20) ? want : (1u << 20))), dim3(256), 0, s, in, out, planes,
+                     IH, IW, PH, PW);
+  return hipGetLastError();
 }
 
 bool fire_weights_null(const DgsFireWeights& f) {
   return f.squeeze_w == nullptr || f.squeeze_b == nullptr || f.expand1_w == nullptr || f.expand1_b == nullptr ||
          f.expand3_w == nullptr || f.expand3_b == nullptr;
+}
+
+// ---- the layer program: a backbone is a table of layers, and ONE plan function and ONE driver walk it
+enum LayerOp { OP_CONV, OP_CONV3X3, OP_FIRE };   // generic convolution; 3 x 3 / 1 / pad 1 (vgg_layer_on_conv3x3 picks the kernel); Fire
+enum PoolOp { POOL_NONE, POOL_3X3S2_FLOOR, POOL_2X2, POOL_3X3S2_CEIL };
+
+struct Layer {
+  LayerOp op;
+  int Cin, Cout, k, stride, pad;   // a Fire module: Cout = 2 E, and 3, 1, 1 -- the map keeps its size
+  int S;                           // a Fire module's squeeze depth, else 0
+  int tap;                         // the tap this layer's output is, or -1
+  PoolOp pool;                     // the pool that follows
+};
+constexpr Layer conv(int Cin, int Cout, int k, int stride, int pad, int tap, PoolOp pool) {
+  return {OP_CONV, Cin, Cout, k, stride, pad, 0, tap, pool};
+}
+constexpr Layer conv3x3(int Cin, int Cout, int tap, PoolOp pool) { return {OP_CONV3X3, Cin, Cout, 3, 1, 1, 0, tap, pool}; }
+constexpr Layer fire(int Cin, int S, int E, int tap, PoolOp pool) { return {OP_FIRE, Cin, 2 * E, 3, 1, 1, S, tap, pool}; }
+
+constexpr int LP_MAX_LAYERS = 13;
+struct Backbone {
+  const char *name, *n_weights;   // for the error texts: "alex", "fifteen"
+  int min_size, n_layers, n_taps;
+  bool equal_bufs;   // both scratch buffers take the largest map of the program (else each the largest map written to it)
+  bool map_limit;    // refuse a first layer whose output has 2^31 elements or more per image
+  Layer layers[LP_MAX_LAYERS];
+};
+
+// AlexNet (networks.py:80-85): five convolutions on the generic kernel, each a tap; 3 x 3 / 2 pools after the first two
+const Backbone ALEX = {"alex", "fifteen", LP_MIN, 5, 5, false, false,
+                       {conv(3, 64, 11, 4, 2, 0, POOL_3X3S2_FLOOR), conv(64, 192, 5, 1, 2, 1, POOL_3X3S2_FLOOR),
+                        conv(192, 384, 3, 1, 1, 2, POOL_NONE), conv(384, 256, 3, 1, 1, 3, POOL_NONE),
+                        conv(256, 256, 3, 1, 1, 4, POOL_NONE)}};
+// VGG16 (networks.py:88-96): thirteen 3 x 3 convolutions; taps after convolutions 2, 4, 7, 10 (each before its 2 x 2
+// pool) and 13
+const Backbone VGG = {"vgg", "thirty-one", V_MIN, 13, 5, true, true,
+                      {conv3x3(3, 64, -1, POOL_NONE), conv3x3(64, 64, 0, POOL_2X2), conv3x3(64, 128, -1, POOL_NONE),
+                       conv3x3(128, 128, 1, POOL_2X2), conv3x3(128, 256, -1, POOL_NONE), conv3x3(256, 256, -1, POOL_NONE),
+                       conv3x3(256, 256, 2, POOL_2X2), conv3x3(256, 512, -1, POOL_NONE), conv3x3(512, 512, -1, POOL_NONE),
+                       conv3x3(512, 512, 3, POOL_2X2), conv3x3(512, 512, -1, POOL_NONE), conv3x3(512, 512, -1, POOL_NONE),
+                       conv3x3(512, 512, 4, POOL_NONE)}};
+// SqueezeNet 1.1 (networks.py:69-77): conv 3 x 3 / 2 (no padding), ReLU, pool, Fire 1, Fire 2, pool, Fire 3, Fire 4,
+// pool, Fire 5 .. 8; pools 3 x 3 / 2 in ceil mode; taps: the first ReLU and Fires 2, 4, 5, 6, 7, 8 (each before its pool).
+// Its two buffers both take the first convolution's output, though the second never holds that much: 529,328,896 bytes
+// for one 1080p pair is what include/dgs_hip.h promises.
+const Backbone SQUEEZE = {"squeeze", "fifty-seven", Q_MIN, 9, 7, true, true,
+                          {conv(3, 64, 3, 2, 0, 0, POOL_3X3S2_CEIL), fire(64, 16, 64, -1, POOL_NONE),
+                           fire(128, 16, 64, 1, POOL_3X3S2_CEIL), fire(128, 32, 128, -1, POOL_NONE),
+                           fire(256, 32, 128, 2, POOL_3X3S2_CEIL), fire(256, 48, 192, 3, POOL_NONE),
+                           fire(384, 48, 192, 4, POOL_NONE), fire(384, 64, 256, 5, POOL_NONE), fire(512, 64, 256, 6, POOL_NONE)}};
+
+int pooled(PoolOp pool, int n) { return pool == POOL_NONE ? n : pool == POOL_3X3S2_FLOOR ? (n - 3) / 2 + 1 : n / 2; }
+
+struct LpipsPlan {
+  int ih[LP_MAX_LAYERS], iw[LP_MAX_LAYERS], oh[LP_MAX_LAYERS], ow[LP_MAX_LAYERS];   // every layer's input and output size
+  size_t off_b, off_partials, total_bytes;   // buffer A at 0, buffer B, the taps' partials
+  LpipsTaps taps;
+};
+
+// Walks the program once, in the driver's order: every map goes to the buffer that does not hold its input, A first.
+// false: an image below the backbone's smallest, no pairs, or sizes the kernels' 32-bit arithmetic does not cover
+bool lpips_plan(const Backbone& B, int W, int H, int n_pairs, LpipsPlan& P) {
+  if (W < B.min_size || H < B.min_size || n_pairs < 1 || n_pairs > 65535 || W > 65536 || H > 65536) return false;
+  const size_t n_img = 2 * (size_t)n_pairs, limit = (size_t)1 << 31;
+  size_t need[2] = {0, 0}, partial = 0;   // floats of the two buffers, doubles of the partials
+  int h = H, w = W, which = 0;
+  auto written = [&](int C) {
+    const size_t map = n_img * C * (size_t)h * w;
+    need[which] = map > need[which] ? map : need[which];
+    which ^= 1;
+  };
+  for (int l = 0; l < B.n_layers; l++) {
+    const Layer& y = B.layers[l];
+    P.ih[l] = h, P.iw[l] = w;
+    h = (h + 2 * y.pad - y.k) / y.stride + 1;
+    w = (w + 2 * y.pad - y.k) / y.stride + 1;
+    P.oh[l] = h, P.ow[l] = w;
+    written(y.Cout);
+    if (y.tap >= 0) {
+      P.taps.first[y.tap] = partial;
+      P.taps.blocks[y.tap] = (int)(((size_t)h * w + 255) / 256);
+      P.taps.hw[y.tap] = (double)h * (double)w;
+      partial += (size_t)n_pairs * P.taps.blocks[y.tap];
+    }
+    if (y.pool != POOL_NONE) {
+      h = pooled(y.pool, h), w = pooled(y.pool, w);
+      written(y.Cout);
+    }
+  }
+  P.taps.n = B.n_taps;
+  // (int32 arithmetic of the kernels: elements of one input image, pixels of a call, elements of one image's largest map)
+  const size_t px0 = (size_t)P.oh[0] * P.ow[0];
+  if ((size_t)3 * H * W >= limit || n_img * px0 >= limit || (B.map_limit && B.layers[0].Cout * px0 >= limit)) return false;
+  if (B.equal_bufs) need[0] = need[1] = need[0] > need[1] ? need[0] : need[1];
+  P.off_b = lp_align(need[0] * sizeof(float));
+  P.off_partials = P.off_b + lp_align(need[1] * sizeof(float));
+  P.total_bytes = P.off_partials + lp_align(partial * sizeof(double));
+  return true;
+}
+
+struct LpipsWeights {   // the three ABI structs, flattened by their entry points
+  const float* layer[LP_MAX_LAYERS][6];   // a convolution's (w, bias), a Fire module's six in DgsFireWeights' order
+  const float* lin[LP_MAX_TAPS];
+};
+
+int lpips_refuse(const Backbone& B, const char* fmt, ...) {
+  char what[128], msg[160];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(what, sizeof what, fmt, ap);
+  va_end(ap);
+  snprintf(msg, sizeof msg, "lpips_%s: %s", B.name, what);
+  return dgs_fail_arg(msg);
+}
+
+// out[pair] = (total, layer 1 .. n_taps) of the pairs (a[i], b[i]).  The first layer reads the two arrays and z-scores
+// them in its gather; every later map is one array of 2 n_pairs images, the b half behind the a half.
+int lpips_run(const Backbone& B, const float* a, const float* b, int n_pairs, int W, int H, const LpipsWeights* w, void* tmp,
+              float* out, dgs_stream_t stream) {
+  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr) return lpips_refuse(B, "null pointer");
+  bool hole = false;
+  for (int l = 0; l < B.n_layers; l++)
+    for (int i = 0; i < (B.layers[l].op == OP_FIRE ? 6 : 2); i++) hole |= w->layer[l][i] == nullptr;
+  for (int t = 0; t < B.n_taps; t++) hole |= w->lin[t] == nullptr;
+  if (hole) return lpips_refuse(B, "null pointer among the %s weight pointers", B.n_weights);
+  if (n_pairs < 1) return lpips_refuse(B, "n_pairs must be at least 1");
+  if (W < B.min_size || H < B.min_size)
+    return lpips_refuse(B, "the smallest image the network accepts is %d x %d (W and H >= %d)", B.min_size, B.min_size, B.min_size);
+  LpipsPlan P;
+  if (!lpips_plan(B, W, H, n_pairs, P)) return lpips_refuse(B, "more than 65535 pairs or more pixels than one call covers");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(tmp);
+  float* bufs[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + P.off_b)};
+  double* partials = reinterpret_cast<double*>(base + P.off_partials);
+  const int n_img = 2 * n_pairs;
+  auto fail = [&](hipError_t e, const char* stage) {
+    char where[64];
+    snprintf(where, sizeof where, "lpips_%s (%s)", B.name, stage);
+    return dgs_fail_hip(e, where);
+  };
+
+  const float* cur = nullptr;   // the map the next kernel reads
+  int which = 0;                // the buffer the next kernel writes
+  for (int l = 0; l < B.n_layers; l++) {
+    const Layer& y = B.layers[l];
+    const float* const* p = w->layer[l];
+    const int ih = P.ih[l], iw = P.iw[l], oh = P.oh[l], ow = P.ow[l];
+    float* dst = bufs[which];
+    which ^= 1;
+    hipError_t e;
+    if (y.op == OP_FIRE) {   // (never the first layer: it reads one array)
+      FireArgs g;
+      g.in0 = cur, g.in1 = cur, g.n_half = n_img;
+      g.sw = p[0], g.sb = p[1], g.w1 = p[2], g.b1 = p[3], g.w3 = p[4], g.b3 = p[5];
+      g.sq_out = nullptr, g.out = dst;
+      g.Cin = y.Cin, g.IH = ih, g.IW = iw, g.S = y.S, g.E1 = y.Cout / 2, g.E3 = y.Cout / 2;
+      e = launch_fire(g, n_img, s);
+    } else {
+      ConvArgs g;
+      g.in0 = (l == 0) ? a : cur;
+      g.in1 = (l == 0) ? b : cur + (size_t)n_pairs * y.Cin * ih * iw;
+      g.n_half = n_pairs;
+      g.w = p[0], g.bias = p[1], g.out = dst;
+      g.Cin = y.Cin, g.IH = ih, g.IW = iw, g.Cout = y.Cout, g.OH = oh, g.OW = ow;
+      g.KH = y.k, g.KW = y.k, g.stride = y.stride, g.pad = y.pad, g.K = y.Cin * y.k * y.k, g.N = n_img * oh * ow;
+      e = (y.op == OP_CONV3X3 && vgg_layer_on_conv3x3(y.Cin, y.Cout)) ? launch_conv3x3(g, n_img, l == 0, s) : launch_conv(g, l == 0, s);
+    }
+    if (e != hipSuccess) return fail(e, y.op == OP_FIRE ? "Fire module" : "convolution");
+    cur = dst;
+    if (y.tap >= 0) {
+      hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[y.tap], (unsigned)n_pairs), dim3(256), 0, s, cur,
+                         (int)n_pairs, y.Cout, oh * ow, w->lin[y.tap], partials + P.taps.first[y.tap]);
+      e = hipGetLastError();
+      if (e != hipSuccess) return fail(e, "layer distance");
+    }
+    if (y.pool != POOL_NONE) {
+      const size_t planes = (size_t)n_img * y.Cout;
+      dst = bufs[which];
+      which ^= 1;
+      e = y.pool == POOL_2X2          ? launch_maxpool2x2(cur, planes, oh, ow, dst, s)
+          : y.pool == POOL_3X3S2_CEIL ? launch_maxpool_ceil(cur, planes, oh, ow, dst, s)
+                                      : launch_maxpool_floor(cur, planes, oh, ow, dst, s);
+      if (e != hipSuccess) return fail(e, "max-pool");
+      cur = dst;
+    }
+  }
+  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGS_OK : fail(e, "finish");
 }
 
 }  // namespace
@@ -1115,81 +1178,6 @@ int dgs_maxpool3x3s2_ceil(const float* in, uint64_t planes, int32_t IH, int32_t 
   return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "maxpool3x3s2_ceil");
 }
 
-size_t dgs_lpips_squeeze_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
-  SqueezePlan P;
-  return squeeze_plan(W, H, n_pairs, P) ? P.total_bytes : 0;
-}
-
-int dgs_lpips_squeeze(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsSqueezeWeights* w,
-                      void* tmp, float* out, dgs_stream_t stream) {
-  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr) return dgs_fail_arg("lpips_squeeze: null pointer");
-  if (w->conv_w == nullptr || w->conv_b == nullptr) return dgs_fail_arg("lpips_squeeze: null pointer among the fifty-seven weight pointers");
-  for (int f = 0; f < 8; f++)
-    if (fire_weights_null(w->fire[f])) return dgs_fail_arg("lpips_squeeze: null pointer among the fifty-seven weight pointers");
-  for (int t = 0; t < 7; t++)
-    if (w->lin[t] == nullptr) return dgs_fail_arg("lpips_squeeze: null pointer among the fifty-seven weight pointers");
-  if (n_pairs < 1) return dgs_fail_arg("lpips_squeeze: n_pairs must be at least 1");
-  if (W < Q_MIN || H < Q_MIN) return dgs_fail_arg("lpips_squeeze: the smallest image the network accepts is 17 x 17 (W and H >= 17)");
-  SqueezePlan P;
-  if (!squeeze_plan(W, H, n_pairs, P)) return dgs_fail_arg("lpips_squeeze: more than 65535 pairs or more pixels than one call covers");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* base = reinterpret_cast<char*>(tmp);
-  float* bufs[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + P.off_b)};
-  double* partials = reinterpret_cast<double*>(base + P.off_partials);
-  const int n_img = 2 * n_pairs;
-  int which = 0;                // the buffer the next kernel writes
-  auto distance = [&](const float* f, int t) {
-    hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[t], (unsigned)n_pairs), dim3(256), 0, s, f, (int)n_pairs,
-                       SQ_TAP_C[t], P.h[t] * P.w[t], w->lin[t], partials + P.taps.first[t]);
-    return hipGetLastError();
-  };
-
-  // the first convolution on the generic kernel: 3 x 3, stride 2, no padding, the z-score fused into its gather
-  ConvArgs c;
-  c.in0 = a, c.in1 = b, c.n_half = n_pairs;
-  c.w = w->conv_w, c.bias = w->conv_b;
-  c.out = bufs[which];
-  c.Cin = 3, c.IH = H, c.IW = W, c.Cout = 64, c.OH = P.h[0], c.OW = P.w[0];
-  c.KH = 3, c.KW = 3, c.stride = 2, c.pad = 0, c.K = 27, c.N = n_img * P.h[0] * P.w[0];
-  hipError_t e = launch_conv(c, true, s);
-  if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (convolution)");
-  const float* cur = bufs[which];
-  which ^= 1;
-  e = distance(cur, 0);
-  if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (layer distance)");
-  e = launch_maxpool_ceil(cur, (size_t)n_img * 64, P.h[0], P.w[0], bufs[which], s);
-  if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (max-pool)");
-  cur = bufs[which];
-  which ^= 1;
-
-  for (int f = 0; f < 8; f++) {
-    const FireShape& F = SQ_FIRES[f];
-    const DgsFireWeights& fw = w->fire[f];
-    FireArgs g;
-    g.in0 = cur, g.in1 = cur, g.n_half = n_img;
-    g.sw = fw.squeeze_w, g.sb = fw.squeeze_b, g.w1 = fw.expand1_w, g.b1 = fw.expand1_b, g.w3 = fw.expand3_w, g.b3 = fw.expand3_b;
-    g.sq_out = nullptr, g.out = bufs[which];
-    g.Cin = F.Cin, g.IH = P.fh[f], g.IW = P.fw[f], g.S = F.S, g.E1 = F.E, g.E3 = F.E;
-    e = launch_fire(g, n_img, s);
-    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (Fire module)");
-    cur = bufs[which];
-    which ^= 1;
-    if (F.tap >= 0) {
-      e = distance(cur, F.tap);
-      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (layer distance)");
-    }
-    if (F.pool) {
-      e = launch_maxpool_ceil(cur, (size_t)n_img * 2 * F.E, P.fh[f], P.fw[f], bufs[which], s);
-      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_squeeze (max-pool)");
-      cur = bufs[which];
-      which ^= 1;
-    }
-  }
-  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
-  e = hipGetLastError();
-  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_squeeze (finish)");
-}
-
 int dgs_conv2d_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
                          const float* bias, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t zscore,
                          float* out, dgs_stream_t stream) {
@@ -1214,70 +1202,6 @@ int dgs_conv2d_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH
   g.KH = KH, g.KW = KW, g.stride = stride, g.pad = pad, g.K = Cin * KH * KW, g.N = (int)(n_img * OH * OW);
   const hipError_t e = launch_conv(g, zscore != 0, reinterpret_cast<hipStream_t>(stream));
   return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "conv2d_bias_relu");
-}
-
-size_t dgs_lpips_alex_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
-  LpipsPlan P;
-  return lpips_plan(W, H, n_pairs, P) ? P.total_bytes : 0;
-}
-
-int dgs_lpips_alex(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsAlexWeights* w,
-                   void* tmp, float* out, dgs_stream_t stream) {
-  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr)
-    return dgs_fail_arg("lpips_alex: null pointer");
-  for (int l = 0; l < 5; l++)
-    if (w->conv_w[l] == nullptr || w->conv_b[l] == nullptr || w->lin[l] == nullptr)
-      return dgs_fail_arg("lpips_alex: null pointer among the fifteen weight pointers");
-  if (n_pairs < 1) return dgs_fail_arg("lpips_alex: n_pairs must be at least 1");
-  if (W < LP_MIN || H < LP_MIN) return dgs_fail_arg("lpips_alex: the smallest image the network accepts is 31 x 31 (W and H >= 31)");
-  LpipsPlan P;
-  if (!lpips_plan(W, H, n_pairs, P)) return dgs_fail_arg("lpips_alex: more than 65535 pairs or more pixels than one call covers");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* base = reinterpret_cast<char*>(tmp);
-  float* buf_a = reinterpret_cast<float*>(base);
-  float* buf_b = reinterpret_cast<float*>(base + P.off_b);
-  double* partials = reinterpret_cast<double*>(base + P.off_partials);
-  const int n_img = 2 * n_pairs;
-
-  const float* cur = nullptr;        // the input of the next convolution (after the first: one array of n_img images)
-  int ih = H, iw = W, n_pool = 0;
-  for (int l = 0; l < 5; l++) {
-    const ConvShape& c = LP_CONVS[l];
-    float* tap = (l == 3) ? buf_b : buf_a;
-    ConvArgs g;
-    g.in0 = (l == 0) ? a : cur;
-    g.in1 = (l == 0) ? b : cur + (size_t)n_pairs * c.Cin * ih * iw;
-    g.n_half = n_pairs;
-    g.w = w->conv_w[l];
-    g.bias = w->conv_b[l];
-    g.out = tap;
-    g.Cin = c.Cin, g.IH = ih, g.IW = iw, g.Cout = c.Cout, g.OH = P.oh[l], g.OW = P.ow[l];
-    g.KH = c.k, g.KW = c.k, g.stride = c.stride, g.pad = c.pad, g.K = c.Cin * c.k * c.k, g.N = n_img * P.oh[l] * P.ow[l];
-    hipError_t e = launch_conv(g, l == 0, s);
-    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_alex (convolution)");
-    const int hw = P.oh[l] * P.ow[l];
-    hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[l], (unsigned)n_pairs), dim3(256), 0, s, tap, (int)n_pairs,
-                       c.Cout, hw, w->lin[l], partials + P.taps.first[l]);
-    e = hipGetLastError();
-    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_alex (layer distance)");
-    cur = tap;
-    ih = P.oh[l], iw = P.ow[l];
-    if (c.pool) {
-      const int ph = P.ph[n_pool], pw = P.pw[n_pool];
-      n_pool++;
-      const size_t planes = (size_t)n_img * c.Cout, total = planes * ph * pw;
-      const size_t want = (total + 255) / 256;
-      hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)(want < (1u << 20) ? want : (1u << 20))), dim3(256), 0, s, tap, buf_b, planes,
-                         ih, iw, ph, pw);
-      e = hipGetLastError();
-      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_alex (max-pool)");
-      cur = buf_b;
-      ih = ph, iw = pw;
-    }
-  }
-  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_alex (finish)");
 }
 
 int dgs_conv3x3_bias_relu(const float* in, int32_t n_img, int32_t Cin, int32_t IH, int32_t IW, const float* weight,
@@ -1309,67 +1233,50 @@ int dgs_maxpool2x2(const float* in, uint64_t planes, int32_t IH, int32_t IW, flo
   return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "maxpool2x2");
 }
 
+// ---- the three backbones: scratch sizes, and the entry points that flatten their weight structs for lpips_run
+size_t dgs_lpips_alex_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
+  LpipsPlan P;
+  return lpips_plan(ALEX, W, H, n_pairs, P) ? P.total_bytes : 0;
+}
+
 size_t dgs_lpips_vgg_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
-  VggPlan P;
-  return vgg_plan(W, H, n_pairs, P) ? P.total_bytes : 0;
+  LpipsPlan P;
+  return lpips_plan(VGG, W, H, n_pairs, P) ? P.total_bytes : 0;
+}
+
+size_t dgs_lpips_squeeze_tmp_bytes(int32_t W, int32_t H, int32_t n_pairs) {
+  LpipsPlan P;
+  return lpips_plan(SQUEEZE, W, H, n_pairs, P) ? P.total_bytes : 0;
+}
+
+int dgs_lpips_alex(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsAlexWeights* w,
+                   void* tmp, float* out, dgs_stream_t stream) {
+  LpipsWeights f;
+  for (int l = 0; w != nullptr && l < 5; l++) f.layer[l][0] = w->conv_w[l], f.layer[l][1] = w->conv_b[l], f.lin[l] = w->lin[l];
+  return lpips_run(ALEX, a, b, n_pairs, W, H, w != nullptr ? &f : nullptr, tmp, out, stream);
 }
 
 int dgs_lpips_vgg(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsVggWeights* w, void* tmp,
                   float* out, dgs_stream_t stream) {
-  if (a == nullptr || b == nullptr || w == nullptr || tmp == nullptr || out == nullptr) return dgs_fail_arg("lpips_vgg: null pointer");
-  for (int l = 0; l < VGG_N; l++)
-    if (w->conv_w[l] == nullptr || w->conv_b[l] == nullptr)
-      return dgs_fail_arg("lpips_vgg: null pointer among the thirty-one weight pointers");
-  for (int t = 0; t < 5; t++)
-    if (w->lin[t] == nullptr) return dgs_fail_arg("lpips_vgg: null pointer among the thirty-one weight pointers");
-  if (n_pairs < 1) return dgs_fail_arg("lpips_vgg: n_pairs must be at least 1");
-  if (W < V_MIN || H < V_MIN) return dgs_fail_arg("lpips_vgg: the smallest image the network accepts is 16 x 16 (W and H >= 16)");
-  VggPlan P;
-  if (!vgg_plan(W, H, n_pairs, P)) return dgs_fail_arg("lpips_vgg: more than 65535 pairs or more pixels than one call covers");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* base = reinterpret_cast<char*>(tmp);
-  float* bufs[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + P.off_b)};
-  double* partials = reinterpret_cast<double*>(base + P.off_partials);
-  const int n_img = 2 * n_pairs;
+  LpipsWeights f;
+  for (int l = 0; w != nullptr && l < 13; l++) f.layer[l][0] = w->conv_w[l], f.layer[l][1] = w->conv_b[l];
+  for (int t = 0; w != nullptr && t < 5; t++) f.lin[t] = w->lin[t];
+  return lpips_run(VGG, a, b, n_pairs, W, H, w != nullptr ? &f : nullptr, tmp, out, stream);
+}
 
-  const float* cur = nullptr;   // the input of the next convolution (after the first: one array of n_img images)
-  int which = 0;                // the buffer the next kernel writes
-  int ih = H, iw = W, cin = 3;
-  for (int l = 0; l < VGG_N; l++) {
-    const int cout = VGG_COUT[l];
-    float* dst = bufs[which];
-    which ^= 1;
-    ConvArgs g;
-    g.in0 = (l == 0) ? a : cur;
-    g.in1 = (l == 0) ? b : cur + (size_t)n_pairs * cin * ih * iw;
-    g.n_half = n_pairs;
-    g.w = w->conv_w[l];
-    g.bias = w->conv_b[l];
-    g.out = dst;
-    g.Cin = cin, g.IH = ih, g.IW = iw, g.Cout = cout, g.OH = ih, g.OW = iw;
-    g.KH = 3, g.KW = 3, g.stride = 1, g.pad = 1, g.K = cin * 9, g.N = n_img * ih * iw;
-    hipError_t e = vgg_layer_on_conv3x3(cin, cout) ? launch_conv3x3(g, n_img, l == 0, s) : launch_conv(g, l == 0, s);
-    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_vgg (convolution)");
-    cur = dst;
-    cin = cout;
-    const int t = VGG_TAP[l];
-    if (t < 0) continue;
-    hipLaunchKernelGGL(layer_distance_kernel, dim3((unsigned)P.taps.blocks[t], (unsigned)n_pairs), dim3(256), 0, s, cur, (int)n_pairs,
-                       cout, ih * iw, w->lin[t], partials + P.taps.first[t]);
-    e = hipGetLastError();
-    if (e != hipSuccess) return dgs_fail_hip(e, "lpips_vgg (layer distance)");
-    if (t < 4) {
-      float* pooled = bufs[which];
-      which ^= 1;
-      e = launch_maxpool2x2(cur, (size_t)n_img * cout, ih, iw, pooled, s);
-      if (e != hipSuccess) return dgs_fail_hip(e, "lpips_vgg (max-pool)");
-      cur = pooled;
-      ih /= 2, iw /= 2;
+int dgs_lpips_squeeze(const float* a, const float* b, int32_t n_pairs, int32_t W, int32_t H, const DgsLpipsSqueezeWeights* w,
+                      void* tmp, float* out, dgs_stream_t stream) {
+  LpipsWeights f;
+  if (w != nullptr) {
+    f.layer[0][0] = w->conv_w, f.layer[0][1] = w->conv_b;
+    for (int i = 0; i < 8; i++) {
+      const DgsFireWeights& m = w->fire[i];
+      const float* six[6] = {m.squeeze_w, m.squeeze_b, m.expand1_w, m.expand1_b, m.expand3_w, m.expand3_b};
+      for (int j = 0; j < 6; j++) f.layer[1 + i][j] = six[j];
     }
+    for (int t = 0; t < 7; t++) f.lin[t] = w->lin[t];
   }
-  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, partials, P.taps, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DGS_OK : dgs_fail_hip(e, "lpips_vgg (finish)");
+  return lpips_run(SQUEEZE, a, b, n_pairs, W, H, w != nullptr ? &f : nullptr, tmp, out, stream);
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@ columns.  `LPIPSSqueezeWeights` takes torchvision's squeezenet1_1 state dict and
 inputs run dgs_lpips_squeeze (csrc/lpips.hip: fire_kernel makes a whole Fire module in one launch, the squeeze map never
 leaves LDS).  tests/golden/lpips_squeeze_golden.npz pins both paths.
 """
+import collections
 import ctypes
 import glob
 import os
@@ -45,6 +46,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .raster_call import _ptr, _stream
 
 MEAN = (-.030, -.088, -.188)                  # networks.py:41-44
 STD = (.458, .448, .450)
@@ -88,29 +90,68 @@ def _as_f32(name, t, shape):
     return t.detach().to(torch.float32).contiguous()
 
 
-class LPIPSWeights:
-    """The fifteen tensors of LPIPS-alex: `conv_w[i]` [Cout,Cin,k,k], `conv_b[i]` [Cout], `lin[i]` [1,C,1,1]."""
-    net_type = "alex"
-    min_size = MIN_SIZE
+# A backbone as a layer program, the table csrc/lpips.hip walks too: per layer its kind ("conv" or "fire"), its index in
+# torchvision's `features`, Cin, Cout (a Fire module: 2 E), kernel, stride, pad, the squeeze depth of a Fire module, the tap
+# it feeds (or None) and the max_pool2d arguments of the pool that follows (or None)
+_Layer = collections.namedtuple("_Layer", "kind index cin cout k stride pad squeeze tap pool")
+_POOL_3X3, _POOL_2X2, _POOL_3X3_CEIL = {"kernel_size": 3, "stride": 2}, {"kernel_size": 2, "stride": 2}, \
+    {"kernel_size": 3, "stride": 2, "ceil_mode": True}
+_ALEX = tuple(_Layer("conv", idx, ci, co, k, stride, pad, None, tap, _POOL_3X3 if pool else None)
+              for tap, (idx, (co, ci, k, stride, pad, pool)) in enumerate(zip(FEATURE_INDEX, CONVS)))
+_VGG = tuple(_Layer("conv", idx, ci, co, 3, 1, 1, None, tap, _POOL_2X2 if tap in (0, 1, 2, 3) else None)
+             for idx, ci, co, tap in zip(VGG_FEATURE_INDEX, VGG_CIN, VGG_COUT, VGG_TAP))
+_SQUEEZE = (_Layer("conv", 0, 3, 64, 3, 2, 0, None, 0, _POOL_3X3_CEIL),) + tuple(
+    _Layer("fire", idx, ci, 2 * e, 3, 1, 1, sq, tap, _POOL_3X3_CEIL if pool else None)
+    for idx, (ci, sq, e), tap, pool in zip(SQUEEZE_FEATURE_INDEX, SQUEEZE_FIRES, SQUEEZE_TAP, SQUEEZE_POOL))
+
+
+def _layer_keys(layer):
+    """[(key below `features.`, shape)] of a layer's tensors, in the order the C ABI holds them."""
+    if layer.kind == "conv":
+        return [(f"{layer.index}.weight", (layer.cout, layer.cin, layer.k, layer.k)), (f"{layer.index}.bias", (layer.cout,))]
+    sq, e = layer.squeeze, layer.cout // 2
+    return [kv for part, shape in zip(FIRE_PARTS, ((sq, layer.cin, 1, 1), (e, sq, 1, 1), (e, sq, 3, 3)))
+            for kv in ((f"{layer.index}.{part}.weight", shape), (f"{layer.index}.{part}.bias", shape[:1]))]
+
+
+def _flat(x):
+    return [x] if torch.is_tensor(x) else [t for y in x for t in _flat(y)]
+
+
+def _moved(x, device):
+    return x.to(device) if torch.is_tensor(x) else type(x)(_moved(y, device) for y in x)
+
+
+class _Weights:
+    """What the three backbones' weights share.  A subclass names its layer program, its ABI struct and the attributes
+    that hold its tensors -- in the struct's order, which is a plain run of pointers."""
+    net_type = min_size = _program = _abi = None
+    _fields = ("conv_w", "conv_b", "lin")
 
     def __init__(self, conv_w, conv_b, lin):
         self.conv_w, self.conv_b, self.lin = list(conv_w), list(conv_b), list(lin)
         self._struct = None
 
     @classmethod
+    def _from_layers(cls, layers, lin):
+        return cls(*zip(*layers), lin)
+
+    def _per_layer(self):
+        """The tensors of each layer of the program: (w, bias), or a Fire module's six."""
+        return list(zip(self.conv_w, self.conv_b))
+
+    @classmethod
     def from_state_dicts(cls, features_sd, lin_sd):
-        """features_sd: torchvision's AlexNet state dict (`features.{0,3,6,8,10}.{weight,bias}`) or the state dict of its
-        `.features` alone (`{0,3,...}.{weight,bias}`).  lin_sd: the published `lin{i}.model.1.weight`, or the reference's
-        renamed `{i}.1.weight` (lpipsPyTorch/modules/utils.py:22-28).  A missing key or a wrong shape raises with the
-        key named."""
-        conv_w, conv_b, lin = [], [], []
-        for i, (idx, (co, ci, k, _, _, _)) in enumerate(zip(FEATURE_INDEX, CONVS)):
-            for part, shape, dst in (("weight", (co, ci, k, k), conv_w), ("bias", (co,), conv_b)):
-                name, t = _pick(features_sd, (f"features.{idx}.{part}", f"{idx}.{part}"), f"features.{idx}.{part}")
-                dst.append(_as_f32(name, t, shape))
-            name, t = _pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight")
-            lin.append(_as_f32(name, t, (1, co, 1, 1)))
-        return cls(conv_w, conv_b, lin)
+        """features_sd: torchvision's state dict of the backbone (`features.{index}.{weight,bias}`, a Fire module's
+        `features.{index}.{squeeze,expand1x1,expand3x3}.{weight,bias}`) or the state dict of its `.features` alone
+        (`{index}. ...`).  lin_sd: the published `lin{i}.model.1.weight`, or the reference's renamed `{i}.1.weight`
+        (lpipsPyTorch/modules/utils.py:22-28).  A missing key or a wrong shape raises with the key named."""
+        layers = [tuple(_as_f32(*_pick(features_sd, (f"features.{key}", key), f"features.{key}"), shape)
+                        for key, shape in _layer_keys(layer)) for layer in cls._program]
+        channels = [layer.cout for layer in cls._program if layer.tap is not None]
+        lin = [_as_f32(*_pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight"), (1, c, 1, 1))
+               for i, c in enumerate(channels)]
+        return cls._from_layers(layers, lin)
 
     @classmethod
     def load(cls, backbone_path, lin_path):
@@ -119,141 +160,57 @@ class LPIPSWeights:
                                     torch.load(lin_path, map_location="cpu", weights_only=True))
 
     def tensors(self):
-        return self.conv_w + self.conv_b + self.lin
+        return _flat([getattr(self, f) for f in self._fields])
 
     @property
     def device(self):
-        return self.conv_w[0].device
+        return _flat(self.conv_w)[0].device
 
     def to(self, device):
-        mv = lambda ts: [t.to(device) for t in ts]
-        return LPIPSWeights(mv(self.conv_w), mv(self.conv_b), mv(self.lin))
+        return type(self)(*(_moved(getattr(self, f), device) for f in self._fields))
 
     def struct(self):
-        """The DgsLpipsAlexWeights of these tensors (they stay alive with this object)."""
+        """The ABI struct of these tensors (they stay alive with this object)."""
         if self._struct is None:
-            s = _lib.DgsLpipsAlexWeights()
-            for i in range(5):
-                s.conv_w[i], s.conv_b[i], s.lin[i] = self.conv_w[i].data_ptr(), self.conv_b[i].data_ptr(), self.lin[i].data_ptr()
+            s = self._abi()
+            slots = ctypes.cast(ctypes.pointer(s), ctypes.POINTER(ctypes.c_void_p))
+            for i, t in enumerate(self.tensors()):
+                slots[i] = t.data_ptr()
             self._struct = s
         return self._struct
 
 
-class LPIPSVggWeights:
-    """The thirty-one tensors of LPIPS-vgg: `conv_w[i]` [Cout,Cin,3,3], `conv_b[i]` [Cout] (13 each), `lin[i]` [1,C,1,1]."""
-    net_type = "vgg"
-    min_size = VGG_MIN_SIZE
-
-    def __init__(self, conv_w, conv_b, lin):
-        self.conv_w, self.conv_b, self.lin = list(conv_w), list(conv_b), list(lin)
-        self._struct = None
-
-    @classmethod
-    def from_state_dicts(cls, features_sd, lin_sd):
-        """features_sd: torchvision's VGG16 state dict (`features.{0,2,5,...,28}.{weight,bias}`) or that of its `.features`
-        alone; lin_sd: the published `lin{i}.model.1.weight` of vgg.pth, or the reference's renamed `{i}.1.weight`.  A
-        missing key or a wrong shape raises with the key named."""
-        conv_w, conv_b, lin = [], [], []
-        for idx, co, ci in zip(VGG_FEATURE_INDEX, VGG_COUT, VGG_CIN):
-            for part, shape, dst in (("weight", (co, ci, 3, 3), conv_w), ("bias", (co,), conv_b)):
-                name, t = _pick(features_sd, (f"features.{idx}.{part}", f"{idx}.{part}"), f"features.{idx}.{part}")
-                dst.append(_as_f32(name, t, shape))
-        for i, c in enumerate(VGG_CHANNELS):
-            name, t = _pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight")
-            lin.append(_as_f32(name, t, (1, c, 1, 1)))
-        return cls(conv_w, conv_b, lin)
-
-    @classmethod
-    def load(cls, backbone_path, lin_path):
-        """The two local checkpoint files (torch.load on the CPU, tensors only)."""
-        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu", weights_only=True),
-                                    torch.load(lin_path, map_location="cpu", weights_only=True))
-
-    def tensors(self):
-        return self.conv_w + self.conv_b + self.lin
-
-    @property
-    def device(self):
-        return self.conv_w[0].device
-
-    def to(self, device):
-        mv = lambda ts: [t.to(device) for t in ts]
-        return LPIPSVggWeights(mv(self.conv_w), mv(self.conv_b), mv(self.lin))
-
-    def struct(self):
-        """The DgsLpipsVggWeights of these tensors (they stay alive with this object)."""
-        if self._struct is None:
-            s = _lib.DgsLpipsVggWeights()
-            for i in range(13):
-                s.conv_w[i], s.conv_b[i] = self.conv_w[i].data_ptr(), self.conv_b[i].data_ptr()
-            for i in range(5):
-                s.lin[i] = self.lin[i].data_ptr()
-            self._struct = s
-        return self._struct
+class LPIPSWeights(_Weights):
+    """The fifteen tensors of LPIPS-alex: `conv_w[i]` [Cout,Cin,k,k], `conv_b[i]` [Cout], `lin[i]` [1,C,1,1]; from
+    torchvision's AlexNet state dict (`features.{0,3,6,8,10}`) and the published `alex.pth`."""
+    net_type, min_size, _program, _abi = "alex", MIN_SIZE, _ALEX, _lib.DgsLpipsAlexWeights
 
 
-class LPIPSSqueezeWeights:
+class LPIPSVggWeights(_Weights):
+    """The thirty-one tensors of LPIPS-vgg: `conv_w[i]` [Cout,Cin,3,3], `conv_b[i]` [Cout] (13 each), `lin[i]` [1,C,1,1];
+    from torchvision's VGG16 state dict (`features.{0,2,5,...,28}`) and the published `vgg.pth`."""
+    net_type, min_size, _program, _abi = "vgg", VGG_MIN_SIZE, _VGG, _lib.DgsLpipsVggWeights
+
+
+class LPIPSSqueezeWeights(_Weights):
     """The fifty-seven tensors of LPIPS-squeeze: `conv_w` [64,3,3,3], `conv_b` [64]; `fire[i]` = (squeeze_w [S,Cin,1,1],
     squeeze_b [S], expand1_w [E,S,1,1], expand1_b [E], expand3_w [E,S,3,3], expand3_b [E]) for the eight Fire modules;
-    `lin[i]` [1,C,1,1] (7)."""
-    net_type = "squeeze"
-    min_size = SQUEEZE_MIN_SIZE
+    `lin[i]` [1,C,1,1] (7); from torchvision's squeezenet1_1 state dict (`features.0`, `features.{3,4,6,7,9,10,11,12}`)
+    and the published `squeeze.pth`."""
+    net_type, min_size, _program, _abi = "squeeze", SQUEEZE_MIN_SIZE, _SQUEEZE, _lib.DgsLpipsSqueezeWeights
+    _fields = ("conv_w", "conv_b", "fire", "lin")
 
     def __init__(self, conv_w, conv_b, fire, lin):
         self.conv_w, self.conv_b, self.fire, self.lin = conv_w, conv_b, [tuple(f) for f in fire], list(lin)
         self._struct = None
 
     @classmethod
-    def from_state_dicts(cls, features_sd, lin_sd):
-        """features_sd: torchvision's squeezenet1_1 state dict (`features.0.{weight,bias}`,
-        `features.{3,4,6,7,9,10,11,12}.{squeeze,expand1x1,expand3x3}.{weight,bias}`) or that of its `.features` alone;
-        lin_sd: the published `lin{i}.model.1.weight` of squeeze.pth, or the reference's renamed `{i}.1.weight`.  A missing
-        key or a wrong shape raises with the key named."""
-        def get(key, shape):
-            name, t = _pick(features_sd, (f"features.{key}", key), f"features.{key}")
-            return _as_f32(name, t, shape)
-        conv_w, conv_b = get("0.weight", (64, 3, 3, 3)), get("0.bias", (64,))
-        fire, lin = [], []
-        for idx, (ci, sq, e) in zip(SQUEEZE_FEATURE_INDEX, SQUEEZE_FIRES):
-            shapes = ((sq, ci, 1, 1), (e, sq, 1, 1), (e, sq, 3, 3))
-            six = []
-            for part, shape in zip(FIRE_PARTS, shapes):
-                six += [get(f"{idx}.{part}.weight", shape), get(f"{idx}.{part}.bias", (shape[0],))]
-            fire.append(tuple(six))
-        for i, c in enumerate(SQUEEZE_CHANNELS):
-            name, t = _pick(lin_sd, (f"lin{i}.model.1.weight", f"{i}.1.weight"), f"lin{i}.model.1.weight")
-            lin.append(_as_f32(name, t, (1, c, 1, 1)))
-        return cls(conv_w, conv_b, fire, lin)
+    def _from_layers(cls, layers, lin):
+        return cls(*layers[0], layers[1:], lin)
 
-    @classmethod
-    def load(cls, backbone_path, lin_path):
-        """The two local checkpoint files (torch.load on the CPU, tensors only)."""
-        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu", weights_only=True),
-                                    torch.load(lin_path, map_location="cpu", weights_only=True))
+    def _per_layer(self):
+        return [(self.conv_w, self.conv_b)] + self.fire
 
-    def tensors(self):
-        return [self.conv_w, self.conv_b] + [t for f in self.fire for t in f] + self.lin
-
-    @property
-    def device(self):
-        return self.conv_w.device
-
-    def to(self, device):
-        return LPIPSSqueezeWeights(self.conv_w.to(device), self.conv_b.to(device),
-                                   [tuple(t.to(device) for t in f) for f in self.fire], [t.to(device) for t in self.lin])
-
-    def struct(self):
-        """The DgsLpipsSqueezeWeights of these tensors (they stay alive with this object)."""
-        if self._struct is None:
-            s = _lib.DgsLpipsSqueezeWeights()
-            s.conv_w, s.conv_b = self.conv_w.data_ptr(), self.conv_b.data_ptr()
-            for i, six in enumerate(self.fire):
-                for (field, _), t in zip(_lib.DgsFireWeights._fields_, six):
-                    setattr(s.fire[i], field, t.data_ptr())
-            for i in range(7):
-                s.lin[i] = self.lin[i].data_ptr()
-            self._struct = s
-        return self._struct
 
 
 def _fire_torch(x, six):
@@ -272,36 +229,22 @@ def _batched(x, y, min_size=MIN_SIZE):
         raise ValueError(f"lpips needs images of at least {min_size} x {min_size} pixels (got {x.shape[-2]} x {x.shape[-1]})")
     return x, y
 
+
 def _features_torch(x, w):
     """The normalised taps of x [N,3,H,W] (networks.py:53-66; five, for squeeze seven) in x's dtype on x's device."""
     t = lambda a: a.to(device=x.device, dtype=x.dtype)
     x = (x - t(torch.tensor(MEAN))[None, :, None, None]) / t(torch.tensor(STD))[None, :, None, None]
     out = []
-    norm = lambda a: a / (torch.sqrt(torch.sum(a ** 2, dim=1, keepdim=True)) + 1e-10)
-    if w.net_type == "squeeze":                             # networks.py:69-77
-        x = F.relu(F.conv2d(x, t(w.conv_w), t(w.conv_b), stride=2))
-        out.append(norm(x))
-        x = F.max_pool2d(x, kernel_size=3, stride=2, ceil_mode=True)
-        for six, tap, pool in zip(w.fire, SQUEEZE_TAP, SQUEEZE_POOL):
-            x = _fire_torch(x, [t(a) for a in six])
-            if tap is not None:
-                out.append(norm(x))
-            if pool:
-                x = F.max_pool2d(x, kernel_size=3, stride=2, ceil_mode=True)
-        return out
-    if w.net_type == "vgg":                                 # networks.py:88-96
-        for i, tap in enumerate(VGG_TAP):
-            x = F.relu(F.conv2d(x, t(w.conv_w[i]), t(w.conv_b[i]), stride=1, padding=1))
-            if tap is not None:
-                out.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10))
-                if tap < 4:
-                    x = F.max_pool2d(x, kernel_size=2, stride=2)
-        return out
-    for i, (_, _, _, stride, pad, pool) in enumerate(CONVS):
-        x = F.relu(F.conv2d(x, t(w.conv_w[i]), t(w.conv_b[i]), stride=stride, padding=pad))
-        out.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10))
-        if pool:
-            x = F.max_pool2d(x, kernel_size=3, stride=2)
+    for layer, tensors in zip(w._program, w._per_layer()):
+        tensors = [t(a) for a in tensors]
+        if layer.kind == "fire":
+            x = _fire_torch(x, tensors)
+        else:
+            x = F.relu(F.conv2d(x, tensors[0], tensors[1], stride=layer.stride, padding=layer.pad))
+        if layer.tap is not None:
+            out.append(x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10))
+        if layer.pool is not None:
+            x = F.max_pool2d(x, **layer.pool)
     return out
 
 
@@ -320,7 +263,7 @@ def lpips_layers(x, y, weights, max_tmp_bytes=MAX_TMP_BYTES):
     """[N,6] = (total, layer 1..5) per pair of x, y ([3,H,W] or [N,3,H,W]) with the backbone of `weights` (LPIPSWeights:
     alex, LPIPSVggWeights: vgg, LPIPSSqueezeWeights: squeeze, whose seven taps give [N,8]).  fp32 device inputs:
     dgs_lpips_alex / dgs_lpips_vgg / dgs_lpips_squeeze on the current stream (the weights must live on that device), no
-    host synchronisation; otherwise the torch expressions in the inputs' dtype.  A vgg or squeeze batch whose scratch
+    host synchronisation; otherwise the torch expressions in the inputs' dtype.  A batch of any backbone whose scratch
     would pass max_tmp_bytes is cut into consecutive calls: a pair's numbers do not depend on the other pairs of its
     call, so the result is the same bit for bit."""
     x, y = _batched(x, y, weights.min_size)
@@ -331,23 +274,18 @@ def lpips_layers(x, y, weights, max_tmp_bytes=MAX_TMP_BYTES):
     x, y = x.contiguous(), y.contiguous()
     L = _lib.lib()
     N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    out = torch.empty((N, 8 if weights.net_type == "squeeze" else 6), dtype=torch.float32, device=x.device)
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    if weights.net_type in ("vgg", "squeeze"):
-        name = "dgs_lpips_" + weights.net_type
-        call, tmp_bytes = getattr(L, name), getattr(L, name + "_tmp_bytes")
-        per_call = N
-        while per_call > 1 and tmp_bytes(W, H, per_call) > max_tmp_bytes:
-            per_call = (per_call + 1) // 2
-        tmp = torch.empty(tmp_bytes(W, H, per_call), dtype=torch.uint8, device=x.device)
-        for i in range(0, N, per_call):
-            n = min(per_call, N - i)
-            _lib.check(call(x[i:i + n].data_ptr(), y[i:i + n].data_ptr(), n, W, H, ctypes.byref(weights.struct()),
-                            tmp.data_ptr(), out[i:i + n].data_ptr(), st), name)
-        return out
-    tmp = torch.empty(L.dgs_lpips_alex_tmp_bytes(W, H, N), dtype=torch.uint8, device=x.device)
-    _lib.check(L.dgs_lpips_alex(x.data_ptr(), y.data_ptr(), N, W, H, ctypes.byref(weights.struct()), tmp.data_ptr(),
-                                out.data_ptr(), st), "dgs_lpips_alex")
+    out = torch.empty((N, len(weights.lin) + 1), dtype=torch.float32, device=x.device)
+    name = "dgs_lpips_" + weights.net_type
+    call, tmp_bytes = getattr(L, name), getattr(L, name + "_tmp_bytes")
+    per_call = N
+    while per_call > 1 and tmp_bytes(W, H, per_call) > max_tmp_bytes:
+        per_call = (per_call + 1) // 2
+    tmp = torch.empty(tmp_bytes(W, H, per_call), dtype=torch.uint8, device=x.device)
+    st = _stream(x.device)
+    for i in range(0, N, per_call):
+        n = min(per_call, N - i)
+        _lib.check(call(_ptr(x[i:i + n]), _ptr(y[i:i + n]), n, W, H, ctypes.byref(weights.struct()), _ptr(tmp),
+                        _ptr(out[i:i + n]), st), name)
     return out
 
 
@@ -363,9 +301,8 @@ def conv2d_bias_relu(x, weight, bias, stride=1, padding=0, zscore=False):
         raise ValueError("conv2d_bias_relu: weight is [Cout,Cin,KH,KW] and bias [Cout]")
     OH, OW = (IH + 2 * padding - KH) // stride + 1, (IW + 2 * padding - KW) // stride + 1
     out = torch.empty((N, Cout, max(OH, 0), max(OW, 0)), dtype=torch.float32, device=x.device)
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.lib().dgs_conv2d_bias_relu(x.data_ptr(), N, Cin, IH, IW, weight.data_ptr(), bias.data_ptr(), Cout, KH, KW,
-                                               int(stride), int(padding), int(bool(zscore)), out.data_ptr(), st),
+    _lib.check(_lib.lib().dgs_conv2d_bias_relu(_ptr(x), N, Cin, IH, IW, _ptr(weight), _ptr(bias), Cout, KH, KW, int(stride),
+                                               int(padding), int(bool(zscore)), _ptr(out), _stream(x.device)),
                "dgs_conv2d_bias_relu")
     return out
 
@@ -381,9 +318,8 @@ def conv3x3_bias_relu(x, weight, bias, zscore=False):
     if tuple(weight.shape) != (Cout, Cin, 3, 3) or tuple(bias.shape) != (Cout,):
         raise ValueError("conv3x3_bias_relu: weight is [Cout,Cin,3,3] and bias [Cout]")
     out = torch.empty((N, Cout, IH, IW), dtype=torch.float32, device=x.device)
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.lib().dgs_conv3x3_bias_relu(x.data_ptr(), N, Cin, IH, IW, weight.data_ptr(), bias.data_ptr(), Cout,
-                                                int(bool(zscore)), out.data_ptr(), st), "dgs_conv3x3_bias_relu")
+    _lib.check(_lib.lib().dgs_conv3x3_bias_relu(_ptr(x), N, Cin, IH, IW, _ptr(weight), _ptr(bias), Cout, int(bool(zscore)),
+                                                _ptr(out), _stream(x.device)), "dgs_conv3x3_bias_relu")
     return out
 
 
@@ -395,8 +331,7 @@ def maxpool2x2(x):
     IH, IW = int(x.shape[-2]), int(x.shape[-1])
     planes = x.numel() // max(IH * IW, 1)
     out = torch.empty(tuple(x.shape[:-2]) + (IH // 2, IW // 2), dtype=torch.float32, device=x.device)
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.lib().dgs_maxpool2x2(x.data_ptr(), planes, IH, IW, out.data_ptr(), st), "dgs_maxpool2x2")
+    _lib.check(_lib.lib().dgs_maxpool2x2(_ptr(x), planes, IH, IW, _ptr(out), _stream(x.device)), "dgs_maxpool2x2")
     return out
 
 
@@ -419,10 +354,8 @@ def fire_bias_relu(x, weights6, return_squeeze=False):
     out = torch.empty((N, E1 + E3, IH, IW), dtype=torch.float32, device=x.device)
     sq = torch.empty((N, S, IH, IW), dtype=torch.float32, device=x.device) if return_squeeze else None
     fw = _lib.DgsFireWeights(*[w.data_ptr() for w in ws])
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.lib().dgs_fire_bias_relu(x.data_ptr(), N, Cin, IH, IW, S, E1, E3, ctypes.byref(fw),
-                                             sq.data_ptr() if return_squeeze else None, out.data_ptr(), st),
-               "dgs_fire_bias_relu")
+    _lib.check(_lib.lib().dgs_fire_bias_relu(_ptr(x), N, Cin, IH, IW, S, E1, E3, ctypes.byref(fw), _ptr(sq), _ptr(out),
+                                             _stream(x.device)), "dgs_fire_bias_relu")
     return (out, sq) if return_squeeze else out
 
 
@@ -435,8 +368,7 @@ def maxpool3x3s2_ceil(x):
     IH, IW = int(x.shape[-2]), int(x.shape[-1])
     planes = x.numel() // max(IH * IW, 1)
     out = torch.empty(tuple(x.shape[:-2]) + (IH // 2, IW // 2), dtype=torch.float32, device=x.device)
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.lib().dgs_maxpool3x3s2_ceil(x.data_ptr(), planes, IH, IW, out.data_ptr(), st), "dgs_maxpool3x3s2_ceil")
+    _lib.check(_lib.lib().dgs_maxpool3x3s2_ceil(_ptr(x), planes, IH, IW, _ptr(out), _stream(x.device)), "dgs_maxpool3x3s2_ceil")
     return out
 
 
