@@ -29,8 +29,8 @@ no-ops (FusedAdam.skip_flag_ptr), so a truncated gradient is never applied.  Suc
 queued (`retry`): TrainingLoop re-runs the view through the exact path as soon as the flag has been read, so every view
 still gets its update (the reference applies every step).
 """
+import collections
 import ctypes
-import os
 
 import torch
 
@@ -50,6 +50,88 @@ class _Pending:
     __slots__ = ("host", "event", "capacity", "speculative", "key", "generation", "request")
 
 
+# What a step that is being RECORDED into a hipGraph is handed from outside the graph's memory pool (_capture_setup): the
+# capacity of the duplicate arrays, the pinned count words, the status words, the address of the scalar block (lambda_t is
+# read from it on the device; words [4:6] hold the address of the step's pinned status slot), the loss kernel's work block
+# and the gradient bucket -- and, for a sharded front, the radii, the screen gradients and the skip word that all fronts of
+# a cloud generation share.  No host bookkeeping happens for such a step.  How far a capture records is the capture's own
+# business: it calls the stages it wants.
+_Capture = collections.namedtuple("_Capture", "capacity host status lambda_ptr work bucket radii means2D skipw",
+                                  defaults=(None, None, None))
+
+
+class _Step:
+    """Everything one iteration owns, by name.  The stages of FusedStep (_cameras -> _forward -> _loss_backward ->
+    _finish) fill it in; nothing else keeps a step's tensors alive.
+
+    LARGE fields -- a capture gives them back to the graph pool (release_large), so the pool holds ONE step's buffers, not
+    one set per captured view.  The launches reach them through raw addresses that outlive the Python references:
+
+        field      raw address in                        last read by
+        geom       prob.geom_state, skip_ptr (one word)  the backward; the optimiser / statistics launch (skip word)
+        image      prob.image_state                      the backward's compositing half
+        binning    prob.binning_state                    the backward's compositing half
+        scratch    io.scratch                            dgs_backward_pose, the last launch of _finish
+        color      out.out_color                         the loss kernel (or the result's 'subframes')
+        depth      out.out_depth                         the depth-smoothness term (or the result's 'depths')
+        dsub       io.dL_dout_color                      the backward's compositing half
+        blur       --                                    the result's 'blur'
+        g_colors   io.dL_dcolors                         the backward's per-Gaussian half
+        g_cov3D    io.dL_dcov3D                          the backward's per-Gaussian half
+
+    The three kinds of raw address and what keeps their memory valid until the last reader has run:
+      * skip_ptr points into the geometry blob and is read by the optimiser launch AFTER the step.  An eager step is
+        FusedStep._keep until the next step begins, so the blob is not handed to a later allocation in between.  A whole
+        captured step (replay) runs that launch inside the graph.  A captured front copies the word into one outside the
+        pool (_Capture.skipw) before it lets go of the blob -- `skip_flag` as a VIEW of the blob would pin all of it.
+      * prob / io hold the addresses of every large field but blur.  After a capture those are blocks of the graph pool
+        that this step no longer owns: they stay valid until the next replay of ANY graph of the pool, and that replay is
+        enqueued behind this step's eager part on the same stream (stream order inside the shared pool).  An eager
+        step's are allocations of the current stream, kept by FusedStep._keep until the next step.
+      * out.status_host_indirect is the address of words [4:6] of the scalar block: no field of the step, it belongs to
+        the graph entry ('hyper') and lives as long as the graph.
+
+    SMALL fields live as long as the step -- until the next one replaces FusedStep._keep -- or, for a recorded step, as
+    long as its graph entry.  A front recorded up to the forward keeps `color` and `depth` too (release_large(keep=)):
+    its loss runs eagerly and reads them as tensors."""
+    LARGE = ("geom", "image", "binning", "scratch", "color", "depth", "dsub", "blur", "g_colors", "g_cov3D")
+    SMALL = (
+        # the request
+        "cap", "request", "gt", "need_blur", "lambda_depth_tv", "shard", "ar", "stats",
+        # alignment and cameras
+        "nu_all", "src", "sel", "uniform", "raw_ptr", "proj", "view", "full", "campos", "nu", "nu_loc",
+        "cam", "K", "K_total", "k0", "P", "H", "W", "Mr", "C", "row", "rrow", "quat", "nrow",
+        # forward
+        "bg", "radii", "prob", "out", "R", "skip_ptr", "skip_flag",
+        # loss and backward
+        "gtc", "work", "losses", "flat", "g_xyz", "g_dc", "g_rest", "g_op", "g_sc", "g_rot", "g_means2D", "g_depth",
+        "depth_tv", "g_view", "g_proj", "io", "chunked")
+    __slots__ = LARGE + SMALL
+
+    def __init__(self, **fields):
+        # (what an eager step's stages read but need not set; every other unset field reads as None too, more slowly)
+        self.cap = self.sel = self.depth = self.skip_ptr = self.skip_flag = self.g_depth = self.depth_tv = None
+        self.g_means2D = None
+        for name, value in fields.items():
+            setattr(self, name, value)
+
+    def __getattr__(self, name):        # only reached for a field that nothing has set yet
+        if name in _Step.__slots__:
+            return None
+        raise AttributeError(name)
+
+    def release_large(self, keep=()):
+        for name in self.LARGE:
+            if name not in keep:
+                setattr(self, name, None)
+
+    def copy(self):
+        new = _Step.__new__(_Step)
+        for name in self.__slots__:
+            setattr(new, name, getattr(self, name))
+        return new
+
+
 class FusedStep:
     def __init__(self, cloud, motion, lambda_hinge=0.0, speculative=True, tile_cull=None):
         if not getattr(cloud, "fused_activations", False):
@@ -64,7 +146,8 @@ class FusedStep:
         self._generation = 0        # bumped when the cloud changes size: counts of older forwards are not learnt
         self._pending = []          # forwards whose counts have not been read back yet
         self._free_hosts = []
-        self._keep = None           # buffers of the last step (the skip flag lives in its geometry blob)
+        self._keep = None           # the last step (_Step: its skip word lives in its geometry blob)
+        self._proj_cache = None     # (the matrix, its version, its contiguous fp32 copy on the device)
         self.last_capacity = None
         # replay() / replay_front() decline (None: the caller enqueues the step eagerly) when the library would run this
         # view's compositing backward in parts if it were enqueued eagerly (dgs_backward_parts > 1: large views).  Inside a
@@ -103,7 +186,7 @@ class FusedStep:
                 pnd.event.synchronize()
             if pnd.event.query():
                 # Every entry owns its pinned words.  An eager step's are written by dgs_forward's own copies; a REPLAYED
-                # step's by a copy of the graph's DgsForwardOut.status_dev enqueued right behind that replay (_track_replay)
+                # step's by a copy of the graph's DgsForwardOut.status_dev enqueued right behind that replay (_track)
                 # -- the pinned block baked into a graph is rewritten by every later replay of the same view while the host
                 # runs several replays ahead, so it can never say which replay overflowed (with two views in
                 # flight a running drop counter read from those blocks went backwards and queued 2^32 - 1 retries).
@@ -118,13 +201,14 @@ class FusedStep:
                 still.append(pnd)
         self._pending = still
 
-    def _track_replay(self, slot, ckey, request, cap, dev):
-        """Behind a replay: the step joins the pending list with the pinned slot that its forward's finalize kernel writes
-        the count / overflow words into (DgsForwardOut.status_host_indirect: the slot's address travelled to the graph
-        through the scalar block, no copy behind the replay)."""
+    def _track(self, host, speculative, ckey, request, cap, dev):
+        """Behind a forward: the step joins the pending list with the pinned words its count / overflow words go to.  An
+        eager step's are written by dgs_forward's own copies.  A replayed step's are the slot that its forward's finalize
+        kernel writes into (DgsForwardOut.status_host_indirect: the slot's address travelled to the graph through the
+        scalar block, no copy behind the replay)."""
         pnd = _Pending()
-        pnd.host = slot
-        pnd.speculative, pnd.key, pnd.generation = True, ckey, self._generation
+        pnd.host = host
+        pnd.speculative, pnd.key, pnd.generation = speculative, ckey, self._generation
         pnd.request, pnd.capacity = request, cap
         pnd.event = torch.cuda.Event()
         pnd.event.record(torch.cuda.current_stream(dev))
@@ -179,18 +263,19 @@ class FusedStep:
             return h
         return torch.zeros(8, dtype=torch.int32).pin_memory()
 
-    def _empty_slice(self, gt, lambda_t, K_total, P, H, W, ct_all, cr_all, nu_raw, need_blur, lambda_depth_tv=0.0,
-                     ar=None):
+    def _empty_slice(self, st, lambda_t):
         """"subframes" sharding with more ranks than subframes: this rank rasterises nothing but takes part in the loss
         block's exchanges; all its gradients are zero."""
         from . import sharding
         cloud, m = self.cloud, self.motion
         dev = cloud._xyz.device
+        gt, K_total, P, H, W, lambda_depth_tv, ar = st.gt, st.K_total, st.P, st.H, st.W, st.lambda_depth_tv, st.ar
+        ct_all, cr_all, nu_raw = m._trans._control_points, m._rot._control_points, m._nu
         f32 = dict(dtype=torch.float32, device=dev)
         color = torch.zeros((0, 3, H, W), **f32)
         _, l1, sm = sharding.subframe_sharded_loss_grad(color, gt.to(dev, torch.float32).contiguous(), K_total,
                                                         float(lambda_t), self.loss_group)
-        # The collectives below are issued in EXACTLY the order run() issues them on a rank that holds subframes -- loss
+        # The collectives below are issued in EXACTLY the order _loss_backward and _finish issue them on a rank that holds subframes -- loss
         # block, depth-smoothness value, gradient bucket (whole or in chunks) -- because RCCL pairs collectives by issue
         # order on the communicator: a different order here would pair a one-element all-reduce with a bucket slice.
         depth_tv = None
@@ -259,11 +344,8 @@ class FusedStep:
         if plan is None:
             return None
         K_total, ckey, cap, cull = plan
-        cloud, m = self.cloud, self.motion
-        gkey = (int(cam_idx), subframe_indice, int(cloud.active_sh_degree), bool(m.is_optimizing()),
-                bool(m.curve_random_sample), cap, self._generation, gt.data_ptr(), bool(cull), bool(dgr.WIDE_RECORDS),
-                tuple(p.data_ptr() for p in cloud.hot_parameters()), tuple(signature),
-                tuple(t.data_ptr() for t in stats) if stats is not None else (), bool(self.always_depth))
+        gkey = self._graph_key(cam_idx, subframe_indice, cap, gt, cull) + (
+            tuple(signature), tuple(t.data_ptr() for t in stats) if stats is not None else ())
         ent = self._graphs.get(gkey)
         if ent is None:
             ent = self._capture(gkey, cam_idx, gt, subframe_indice, cap, optimizer, tail, stats)
@@ -296,18 +378,32 @@ class FusedStep:
         if plan is None:
             return None
         K_total, ckey, cap, cull = plan
-        cloud, m = self.cloud, self.motion
         chunks = 1 if ar is None else int(ar.get("chunks", 1))
-        gkey = ("front", int(cam_idx), subframe_indice, int(cloud.active_sh_degree), bool(m.is_optimizing()),
-                bool(m.curve_random_sample), cap, self._generation, gt.data_ptr(), bool(cull), bool(dgr.WIDE_RECORDS),
-                tuple(p.data_ptr() for p in cloud.hot_parameters()), chunks, float(self.lambda_hinge),
-                None if shard is None else (int(shard[0]), int(shard[1])), bool(self.always_depth))
+        gkey = ("front",) + self._graph_key(cam_idx, subframe_indice, cap, gt, cull) + (
+            chunks, float(self.lambda_hinge), None if shard is None else (int(shard[0]), int(shard[1])))
         ent = self._graphs.get(gkey)
         if ent is None:
             ent = self._capture_front(gkey, cam_idx, gt, subframe_indice, cap, ar, K_total, shard)
         hbuf, hev = self._scalar_slot(ent, lambda_t, background, uniform)
         self._launch(ent, hbuf, hev, ckey, (cam_idx, subframe_indice), cap, background_dev, uniform_dev)
-        return ent["finish"](float(lambda_t))
+        return ent["finish"](ent["step"], float(lambda_t))
+
+    def _graph_key(self, cam_idx, subframe_indice, cap, gt, cull):
+        """What every captured step bakes in; replay() and replay_front() add their own."""
+        cloud, m = self.cloud, self.motion
+        return (int(cam_idx), subframe_indice, int(cloud.active_sh_degree), bool(m.is_optimizing()),
+                bool(m.curve_random_sample), cap, self._generation, gt.data_ptr(), bool(cull), bool(dgr.WIDE_RECORDS),
+                tuple(p.data_ptr() for p in cloud.hot_parameters()), bool(self.always_depth))
+
+    def _resume(self, front, lambda_now):
+        """The eager part behind a replayed front (the hook of its graph entry, 'finish').  A front recorded up to the
+        forward goes on in a copy of the recorded step: what its loss and backward allocate lives until the next step,
+        like an eager step's, not as long as the graph entry."""
+        if front.shard is None:
+            return self._finish(front)
+        st = front.copy()
+        self._loss_backward(st, lambda_now)
+        return self._finish(st)
 
     def _replay_plan(self, cam_idx, subframe_indice, shard=None):
         """What replay() and replay_front() settle before they look up a graph: (K_total, the capacity key, the capacity
@@ -367,14 +463,14 @@ class FusedStep:
         if uniform_dev is not None and self.motion.curve_random_sample and f > 2:
             ent["hyper"][48:48 + f - 2].copy_(uniform_dev.reshape(f - 2))
         ent["graph"].replay()
-        self._track_replay(slot, ckey, request, cap, dev)
+        self._track(slot, True, ckey, request, cap, dev)
         self.last_capacity = cap
         self.replayed += 1
 
     def _capture_setup(self, cap, optimizer=None):
         """What both captures allocate OUTSIDE the capture pool before they record: the scalar block, the pinned count
         words, the status words, the drop counter, the loss kernel's work block and the gradient bucket.  Returns (ent,
-        the run() arguments of a capture, the background and the alignment jitter as views of the scalar block)."""
+        the _Capture record of these, the background and the alignment jitter as views of the scalar block)."""
         cloud, m = self.cloud, self.motion
         dev = cloud._xyz.device
         f = m.n_subframes
@@ -400,8 +496,7 @@ class FusedStep:
         if self._bucket is None or self._bucket[0] != self._generation or self._bucket[1] != n_bucket:
             self._bucket = (self._generation, n_bucket, torch.empty(n_bucket, dtype=torch.float32, device=dev))
         ent["work"] = torch.zeros(8, dtype=torch.float32, device=dev)
-        cap_args = {"capacity": cap, "host": host, "status": ent["status"], "lambda_ptr": hyper.data_ptr(),
-                    "work": ent["work"], "bucket": self._bucket[2]}
+        cap_args = _Capture(int(cap), host, ent["status"], hyper.data_ptr(), ent["work"], self._bucket[2])
         params = list(cloud.hot_parameters()) + (list(m.parameters()) if m.is_optimizing() else [])
         if optimizer is not None:
             optimizer.ensure_state(params)
@@ -428,48 +523,55 @@ class FusedStep:
             self._front_shared = (skey, torch.empty((K_total, P), dtype=torch.int32, device=dev),
                                   torch.empty((K_total, P, 3), dtype=torch.float32, device=dev),
                                   torch.zeros(1, dtype=torch.int32, device=dev))
-        cap_args.update(split="composite" if shard is None else "forward", radii=self._front_shared[1],
-                        means2D=self._front_shared[2], skipw=self._front_shared[3], tail=None)
+        cap_args = cap_args._replace(radii=self._front_shared[1], means2D=self._front_shared[2], skipw=self._front_shared[3])
+        st = _Step(cap=cap_args, request=(cam_idx, subframe_indice), gt=gt, need_blur=False, lambda_depth_tv=0.0,
+                   shard=shard, ar=ar)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
-                front = self.run(cam_idx, 0.0, gt, bg, subframe_indice, uniform=uniform, _cap=cap_args, ar=ar, shard=shard)
+            with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"), torch.no_grad():
+                # "views" sharding: up to the first collective, the reduction of the gradient bucket.  "subframes" sharding
+                # (shard): that is the loss block, so the front ends with the forward.
+                self._cameras(st, uniform)
+                self._forward(st, bg)
+                if shard is None:
+                    self._loss_backward(st, 0.0)
+                # the skip word to one of its own, outside the pool (as a view it would pin the whole geometry blob)
+                cap_args.skipw.copy_(st.skip_flag)
+                st.skip_flag = cap_args.skipw
         except RuntimeError as ex:
             raise CaptureRefused(str(ex)) from ex
-        # the step's large buffers go back to the pool (the other views' captures re-use the blocks); finish() reaches them
-        # through the raw pointers of its DgsProblem / DgsBackwardIO -- valid until the next replay of ANY graph of the pool,
-        # which is enqueued after this step's eager part on the same stream
-        front["big"][0] = None
-        if "fwd_big" in front:
-            front["fwd_big"][0] = None
-        ent["finish"], ent["keep"] = front["finish"], front["_keep"]
+        # the step's large buffers go back to the pool (the other views' captures re-use the blocks): _Step has the rules
+        st.release_large(keep=() if shard is None else ("color", "depth"))
+        ent["step"], ent["finish"] = st, self._resume
         return self._register(gkey, ent, graph)
 
     def _capture(self, gkey, cam_idx, gt, subframe_indice, cap, optimizer, tail, stats=None):
         dev = self.cloud._xyz.device
         ent, cap_args, bg, uniform, params = self._capture_setup(cap, optimizer)
-        hyper = ent["hyper"]
-        cap_args["tail"] = (lambda fr: tail(fr, hyper.data_ptr() + 4 * 8)) if tail is not None else None
+        st = _Step(cap=cap_args, request=(cam_idx, subframe_indice), gt=gt, need_blur=False, lambda_depth_tv=0.0,
+                   stats=stats)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
-            fr = self.run(cam_idx, 0.0, gt, bg, subframe_indice, uniform=uniform, _cap=cap_args, stats=stats)
+        with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"), torch.no_grad():
+            self._cameras(st, uniform)
+            self._forward(st, bg)
+            self._loss_backward(st, 0.0)
+            fr = self._finish(st)
+            if tail is not None:
+                tail(fr, ent["hyper"].data_ptr() + 4 * 8)
         # What a replay leaves behind for the host is the two loss values, the count words (pinned) and the gradients of
-        # the parameters (the first and the last allocated outside the pool, by _capture_setup); everything else the step allocated
-        # is released to the pool here, so that the captures of the other views re-use the same blocks (every replay is a
-        # complete step: nothing of one replay is read after the next has started) -- the pool holds ONE step's buffers,
-        # not one set per view.
+        # the parameters (the first and the last allocated outside the pool, by _capture_setup).  Every replay is a complete
+        # step, so everything else goes back to the pool with `st` (here and in _register).
         ent["result"] = {"losses": fr["losses"], "K": fr["K"], "skip_flag_ptr": fr["skip_flag_ptr"], "blur": None,
                          "radii": None, "viewspace_grad": None, "subframes": None, "depths": None, "depth_tv": None}
         ent["grads"] = [(p, p.grad) for p in params if p.grad is not None]
-        del fr
         return self._register(gkey, ent, graph)
 
     # ------------------------------------------------------------------------------------------------- the step
     @torch.no_grad()
     def run(self, cam_idx, lambda_t, gt, background, subframe_indice="all", need_blur=False, uniform=None,
-            lambda_depth_tv=0.0, shard=None, exact=False, need_depth=False, _cap=None, ar=None, stats=None):
+            lambda_depth_tv=0.0, shard=None, exact=False, need_depth=False, ar=None, stats=None):
         """gt: [3,H,W] ground truth of view cam_idx (already tone-mapped / noised by the caller); background: [3].
         lambda_depth_tv > 0 adds the reference's optional depth-smoothness term (train.py:150-153,
         utils/loss_utils.py:66-78): its gradient on the K depth images is formed with a few torch ops and handed to the
@@ -488,286 +590,266 @@ class FusedStep:
         stats = (max_radii2D, xyz_gradient_accum, denom): the cloud's densification accumulators ([P] float32); the
         backward then updates them itself (DgsBackwardIO.stats_*, exactly densify_stats.add_densification_stats_subframes
         on this step's screen gradients) and 'viewspace_grad' comes back None -- the [K,P,3] gradient is never stored.
-        _cap: internal, set by replay() while the step is being CAPTURED into a hipGraph -- the capacity, the pinned count
-        words, the device words lambda_t is read from and the tail (statistics + optimiser launch) to enqueue; no host
-        bookkeeping happens then.
+        The step is four stages on one _Step (which states what lives how long); a capture (replay, replay_front) records a
+        prefix of the same stages and the eager part behind a replayed front runs the rest (_resume).
         Returns a dict: 'losses' (device float32 [2]: L1(blur, gt), smoothness -- no host read), 'blur' ([3,H,W] if
         need_blur), 'radii' [K,P] int32, 'viewspace_grad' [K,P,3], 'K', 'skip_flag_ptr' (int or None)."""
+        st = _Step(request=(cam_idx, subframe_indice), gt=gt, need_blur=need_blur, lambda_depth_tv=lambda_depth_tv,
+                   shard=shard, ar=ar, stats=stats)
+        self._cameras(st, uniform)
+        if st.K == 0:
+            return self._empty_slice(st, lambda_t)
+        self._forward(st, background, exact, need_depth)
+        self._loss_backward(st, lambda_t)
+        return self._finish(st)
+
+    def _cameras(self, st, uniform):
+        """Stage 1: alignment -> nu (all f candidates, then the requested subset) -> the K cameras -> this rank's slice of
+        them ("subframes" sharding; K == 0: the caller goes to _empty_slice)."""
         L = _lib.lib()
         cloud, m = self.cloud, self.motion
         dev = cloud._xyz.device
-        stream_obj = torch.cuda.current_stream(dev)
         stream = _stream(dev)
         f32 = dict(dtype=torch.float32, device=dev)
         f = m.n_subframes
-        cam = int(cam_idx)
-
-        # ---- alignment -> nu (all f candidates), then the requested subset
+        cam_idx, subframe_indice = st.request
+        cam = st.cam = int(cam_idx)
         nu_raw = m._nu
-        nu_all = torch.empty(f, **f32)
-        src = torch.empty(f, dtype=torch.int32, device=dev)
-        nrow = nu_raw.shape[1] if nu_raw.ndim == 2 else 0
-        raw_ptr = _ptr(nu_raw, cam * nrow) if nrow > 0 else None
+        nu_all = st.nu_all = torch.empty(f, **f32)
+        st.src = torch.empty(f, dtype=torch.int32, device=dev)
+        nrow = st.nrow = nu_raw.shape[1] if nu_raw.ndim == 2 else 0
+        st.raw_ptr = _ptr(nu_raw, cam * nrow) if nrow > 0 else None
         if uniform is None and m.curve_random_sample and nrow > 0:
             uniform = torch.rand(nrow, **f32)
         if not m.curve_random_sample:
             uniform = None
-        _lib.check(L.dgs_alignment_forward(raw_ptr, _ptr(uniform), f, f, _ptr(nu_all), _ptr(src), stream),
+        st.uniform = uniform
+        _lib.check(L.dgs_alignment_forward(st.raw_ptr, _ptr(uniform), f, f, _ptr(nu_all), _ptr(st.src), stream),
                    "dgs_alignment_forward")
-        sel = None
         if isinstance(subframe_indice, str) and subframe_indice == "all":
             nu = nu_all
         else:
             if isinstance(subframe_indice, int):     # scene/motion.py:129-131 (1 selects index 0)
-                sel = self._linspace_sel(f, subframe_indice, dev)
+                st.sel = self._linspace_sel(f, subframe_indice, dev)
             else:
-                sel = torch.as_tensor(subframe_indice, device=dev).long()
-            nu = nu_all[sel].contiguous()
+                st.sel = torch.as_tensor(subframe_indice, device=dev).long()
+            nu = nu_all[st.sel].contiguous()
         K = nu.shape[0]
 
-        # ---- cameras
         ct_all, cr_all = m._trans._control_points, m._rot._control_points
-        C = ct_all.shape[1] - 1
-        row = cam * (C + 1) * 3                       # this view's curve in the translation control points ...
-        quat = int(cr_all.shape[-1] == 4)             # ... and in the rotation ones ([C+1,4]: quaternion curve)
-        rrow = cam * (C + 1) * cr_all.shape[-1]
+        C = st.C = ct_all.shape[1] - 1
+        row = st.row = cam * (C + 1) * 3              # this view's curve in the translation control points ...
+        quat = st.quat = int(cr_all.shape[-1] == 4)   # ... and in the rotation ones ([C+1,4]: quaternion curve)
+        rrow = st.rrow = cam * (C + 1) * cr_all.shape[-1]
         # (stored as a transposed view: made contiguous ONCE -- a 16-float copy kernel per step is a launch and a gap on the
         # device's timeline, 2 % of a cfg2 step)
         pm = m.ref_cam.projection_matrix
-        pc = getattr(self, "_proj_cache", None)
+        pc = self._proj_cache
         if pc is None or pc[0] is not pm or pc[1] != pm._version or pc[2].device != dev:
             pc = self._proj_cache = (pm, pm._version, pm.to(dev, torch.float32).contiguous().clone())
-        proj = pc[2]
+        proj = st.proj = pc[2]
         view = torch.empty((K, 4, 4), **f32)
         full = torch.empty((K, 4, 4), **f32)
         campos = torch.empty((K, 3), **f32)
         _lib.check(L.dgs_pose_forward(_ptr(ct_all, row), _ptr(cr_all, rrow), _ptr(nu), _ptr(proj), C, K, quat, _ptr(view),
                                       _ptr(full), _ptr(campos), stream), "dgs_pose_forward")
 
-        K_total, k0 = K, 0
+        st.K_total, st.k0 = K, 0
         nu_loc = nu
-        if shard is not None:
+        if st.shard is not None:
             from .sharding import shard_range
-            k0, k1 = shard_range(K_total, int(shard[0]), int(shard[1]))
+            st.k0, k1 = shard_range(K, int(st.shard[0]), int(st.shard[1]))
+            k0 = st.k0
             view, full, campos, nu_loc = view[k0:k1], full[k0:k1], campos[k0:k1], nu[k0:k1]   # (contiguous row slices)
             K = k1 - k0
-        # ---- forward
-        P = cloud._xyz.shape[0]
-        H, W = int(m.ref_cam.image_height), int(m.ref_cam.image_width)
-        if K == 0:
-            return self._empty_slice(gt, lambda_t, K_total, P, H, W, ct_all, cr_all, nu_raw, need_blur, lambda_depth_tv,
-                                     ar)
-        rest = cloud._features_rest if cloud._features_rest.shape[1] > 0 else None
-        Mr = 0 if rest is None else rest.shape[1]
-        color = torch.empty((K, 3, H, W), **f32)
+        st.view, st.full, st.campos, st.nu, st.nu_loc, st.K = view, full, campos, nu, nu_loc, K
+        st.P, st.Mr = cloud._xyz.shape[0], cloud._features_rest.shape[1]
+        st.H, st.W = int(m.ref_cam.image_height), int(m.ref_cam.image_width)
+
+    def _forward(self, st, background, exact=False, need_depth=False):
+        """Stage 2: the state blobs, the problem, the forward (capacity None: the exact two-phase one, one blocking read of
+        the count -- also how the first capacity is learnt) and the skip word."""
+        L = _lib.lib()
+        cloud, m = self.cloud, self.motion
+        dev = cloud._xyz.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        cap, K, P, H, W = st.cap, st.K, st.P, st.H, st.W
+        st.color = torch.empty((K, 3, H, W), **f32)
         # the depth images are rendered only if somebody reads them (the reference always renders them, and its default
         # loss, lambda_depth_tv = 0, never looks at them: train.py:150-153)
-        depth = torch.empty((K, 1, H, W), **f32) if (need_depth or self.always_depth or lambda_depth_tv > 0.0) else None
-        radii = (torch.empty((K, P), dtype=torch.int32, device=dev) if (_cap is None or "radii" not in _cap)
-                 else _cap["radii"][:K])
-        geom = torch.empty(L.dgs_geom_state_bytes(P, K), dtype=torch.uint8, device=dev)
-        image = torch.empty(L.dgs_image_state_bytes(W, H, K), dtype=torch.uint8, device=dev)
-        bg = background.to(dev, torch.float32).contiguous()
+        if need_depth or self.always_depth or st.lambda_depth_tv > 0.0:
+            st.depth = torch.empty((K, 1, H, W), **f32)
+        st.radii = (torch.empty((K, P), dtype=torch.int32, device=dev) if (cap is None or cap.radii is None)
+                    else cap.radii[:K])
+        geom = st.geom = torch.empty(L.dgs_geom_state_bytes(P, K), dtype=torch.uint8, device=dev)
+        st.image = torch.empty(L.dgs_image_state_bytes(W, H, K), dtype=torch.uint8, device=dev)
+        st.bg = background.to(dev, torch.float32).contiguous()
         cull = dgr.TILE_CULL if self.tile_cull is None else bool(self.tile_cull)
-        prob = raster_call.cloud_problem(cloud, K, view, full, campos, H, W, m.ref_cam.FoVx, m.ref_cam.FoVy, bg, cull,
-                                         geom, image)
-        key = (cam, K_total, k0)
-        if _cap is None:
+        st.prob = raster_call.cloud_problem(cloud, K, st.view, st.full, st.campos, H, W, m.ref_cam.FoVx, m.ref_cam.FoVy,
+                                            st.bg, cull, geom, st.image)
+        key = (st.cam, st.K_total, st.k0)
+        if cap is None:
             host = self._host_words()
             self._poll()
-            cap = self._capacity(key) if (self.speculative and not exact) else None
-            pnd = _Pending()
-            pnd.host, pnd.speculative, pnd.key, pnd.generation = host, cap is not None, key, self._generation
-            pnd.request = (cam_idx, subframe_indice)
-            out = raster_call.forward_out(color, depth, radii, host)
+            capacity = self._capacity(key) if (self.speculative and not exact) else None
+            st.out = raster_call.forward_out(st.color, st.depth, st.radii, host)
         else:
-            host, cap, pnd = _cap["host"], int(_cap["capacity"]), None
-            out = raster_call.forward_out(color, depth, radii, host, drop_counter=self._drop_counter(dev),
-                                          status_dev=_cap["status"],
-                                          status_host_indirect=_cap["lambda_ptr"] + 16)   # words [4:6] of the scalar block
-        # capacity None: the exact two-phase forward, one blocking read of the count (also how the first capacity is learnt)
-        R, binning = raster_call.forward(dev, prob, out, host, cap)
-        skip_ptr = None if cap is None else geom.data_ptr() + raster_call.skip_word_offset(P, W, H, K)
-        if pnd is not None:
-            pnd.capacity = R
-            pnd.event = torch.cuda.Event()
-            pnd.event.record(stream_obj)
-            self._pending.append(pnd)
-        self.last_capacity = R
+            host, capacity = cap.host, cap.capacity
+            st.out = raster_call.forward_out(st.color, st.depth, st.radii, host, drop_counter=self._drop_counter(dev),
+                                             status_dev=cap.status,
+                                             status_host_indirect=cap.lambda_ptr + 16)   # words [4:6] of the scalar block
+        st.R, st.binning = raster_call.forward(dev, st.prob, st.out, host, capacity)
+        if cap is None:
+            self._track(host, capacity is not None, key, st.request, st.R, dev)
+        self.last_capacity = st.R
+        if capacity is not None:
+            off = raster_call.skip_word_offset(P, W, H, K)
+            st.skip_ptr = geom.data_ptr() + off
+            st.skip_flag = geom[off:off + 4].view(torch.int32)
 
-        # The forward's three state blobs and the skip word, held through one-element lists: a captured front empties the
-        # first after the capture, and what follows reaches them through the raw pointers of prob / io only.
-        fwd_big = [(geom, image, binning)]
-        fwd_skip = [None]
-        if skip_ptr is not None:
-            off = skip_ptr - geom.data_ptr()
-            fwd_skip[0] = geom[off:off + 4].view(torch.int32)
-            if _cap is not None and _cap.get("split") == "forward":     # (the view would pin the whole geometry blob)
-                _cap["skipw"].copy_(fwd_skip[0])
-                fwd_skip[0] = _cap["skipw"]
-        del geom, image, binning
-        bucket = raster_call.cloud_bucket(P, Mr)      # the layout of this step's gradient bucket
+    def _loss_backward(self, st, lambda_t):
+        """Stage 3: the loss and the launches up to the first collective of the gradient reduction.  lambda_t is the
+        scheduled weight of THIS call (a recorded step reads it from the scalar block on the device instead)."""
+        L = _lib.lib()
+        cloud = self.cloud
+        dev = cloud._xyz.device
+        stream = _stream(dev)       # (the stream of THIS call: behind a replayed front that is the caller's, not the capture's)
+        f32 = dict(dtype=torch.float32, device=dev)
+        cap, shard, K, K_total, P, H, W = st.cap, st.shard, st.K, st.K_total, st.P, st.H, st.W
+        # ---- loss: blur, both values and dL/dsubframes in one pass (train.py:143-165 image terms)
+        gtc = st.gtc = st.gt.to(dev, torch.float32).contiguous()
+        blur = torch.empty((3, H, W), **f32)
+        dsub = torch.empty((K, 3, H, W), **f32)
+        # dgs_blur_loss_grad's work area: [l1, smooth | accumulators, counter]
+        work = st.work = torch.empty(8, **f32) if cap is None else cap.work
+        st.losses = work[:2]
+        if cap is not None and shard is None:      # the scheduled weight is read from device memory when the replayed kernel runs
+            _lib.check(L.dgs_blur_loss_grad_dev(_ptr(st.color), _ptr(gtc), K, 3, H * W, ctypes.c_void_p(cap.lambda_ptr),
+                                                None, _ptr(blur), _ptr(dsub), _ptr(work), stream),
+                       "dgs_blur_loss_grad_dev")
+        elif shard is None:
+            _lib.check(L.dgs_blur_loss_grad(_ptr(st.color), _ptr(gtc), K, 3, H * W, float(lambda_t), None, _ptr(blur),
+                                            _ptr(dsub), _ptr(work), stream), "dgs_blur_loss_grad")
+        else:   # the loss block across the ranks holding the view's other subframes
+            from . import sharding
+            dsub, l1, sm = sharding.subframe_sharded_loss_grad(st.color, gtc, K_total, float(lambda_t), self.loss_group)
+            dsub = dsub.contiguous()
+            st.losses = torch.stack([l1.reshape(()), sm.reshape(())]).float()
+            blur = None
+        st.blur, st.dsub = blur, dsub
 
-        # Everything after the forward.  Eager steps run it right away.  A "subframes"-sharded step replayed by replay_front
-        # captures only what precedes it (its first collective is the loss block) and calls it after every replay; a
-        # "views"-sharded one captures on, up to the cut inside (finish()).
-        def after_forward(lambda_now=None):
-            stream_obj = torch.cuda.current_stream(dev)       # (the stream of THIS call, not of a capture)
-            stream = ctypes.c_void_p(stream_obj.cuda_stream)
-            lam = float(lambda_t if lambda_now is None else lambda_now)     # (a replayed front hands in this step's weight)
-            # ---- loss: blur, both values and dL/dsubframes in one pass (train.py:143-165 image terms)
-            gtc = gt.to(dev, torch.float32).contiguous()
-            blur = torch.empty((3, H, W), **f32)
-            dsub = torch.empty((K, 3, H, W), **f32)
-            # dgs_blur_loss_grad's work area: [l1, smooth | accumulators, counter]
-            work = torch.empty(8, **f32) if _cap is None else _cap["work"]
-            losses = work[:2]
-            if _cap is not None and shard is None:      # the scheduled weight is read from device memory when the replayed kernel runs
-                _lib.check(L.dgs_blur_loss_grad_dev(_ptr(color), _ptr(gtc), K, 3, H * W, ctypes.c_void_p(_cap["lambda_ptr"]),
-                                                    None, _ptr(blur), _ptr(dsub), _ptr(work), stream),
-                           "dgs_blur_loss_grad_dev")
-            elif shard is None:
-                _lib.check(L.dgs_blur_loss_grad(_ptr(color), _ptr(gtc), K, 3, H * W, lam, None, _ptr(blur),
-                                                _ptr(dsub), _ptr(work), stream), "dgs_blur_loss_grad")
-            else:   # the loss block across the ranks holding the view's other subframes
-                from . import sharding
-                dsub, l1, sm = sharding.subframe_sharded_loss_grad(color, gtc, K_total, lam, self.loss_group)
-                dsub = dsub.contiguous()
-                losses = torch.stack([l1.reshape(()), sm.reshape(())]).float()
-                blur = None
+        # ---- backward: one flat gradient bucket in optimiser-group order (as _RasterizeCloudK.backward)
+        bucket = raster_call.cloud_bucket(P, st.Mr)
+        flat = st.flat = torch.empty(bucket.size, **f32) if cap is None else cap.bucket
+        assert flat.numel() == bucket.size
+        st.g_xyz, st.g_dc, st.g_rest, st.g_op, st.g_sc, st.g_rot = bucket.views(flat, [
+            (P, 3), cloud._features_dc.shape, cloud._features_rest.shape, cloud._opacity.shape, (P, 3), (P, 4)])
+        if st.stats is None:
+            st.g_means2D = (torch.empty((K, P, 3), **f32) if (cap is None or cap.means2D is None) else cap.means2D[:K])
+        if st.lambda_depth_tv > 0.0:
+            from . import losses as _losses
+            # tv_loss is a mean over the view's K depth images of per-image terms (utils/loss_utils.py:66-78): a rank
+            # holding K of the K_total subframes contributes K / K_total of it and needs no other rank's depths
+            share = K / float(K_total)
+            with torch.enable_grad():
+                dleaf = st.depth.detach().requires_grad_(True)
+                depth_tv = _losses.tv_loss(dleaf) * share
+                g_depth, = torch.autograd.grad(float(st.lambda_depth_tv) * depth_tv, dleaf)
+            st.g_depth, st.depth_tv = g_depth.contiguous(), depth_tv.detach()
+            if shard is not None:
+                import torch.distributed as dist
+                dist.all_reduce(st.depth_tv, group=self.loss_group)   # the value only (logging); the gradient is local
+        st.io, own = raster_call.backward_io(
+            st.R, st.radii, dsub, st.g_depth, means3D=st.g_xyz, means2D=st.g_means2D, sh=st.g_dc,
+            sh_rest=st.g_rest if st.Mr > 0 else None, opacity=st.g_op, scales=st.g_sc, rotations=st.g_rot,
+            # sharded: the ranks' gradients are summed, so the hinge term is added by one of them only
+            opacity_hinge_scale=self.lambda_hinge / max(P, 1) if (shard is None or int(shard[0]) == 0) else 0.0,
+            stats=st.stats, stats_K_total=K_total)
+        st.scratch, st.g_colors, st.g_cov3D = own["scratch"], own["colors"], own["cov3D"]
+        st.g_view, st.g_proj = own["viewmatrix"], own["projmatrix"]
+        # a sharded run reduces the bucket in Gaussian-index chunks, each behind its part of the per-Gaussian half (_finish)
+        st.chunked = not (st.ar is None or int(st.ar.get("chunks", 1)) <= 1 or P < 512)
+        if st.chunked:
+            _lib.check(L.dgs_backward_composite(ctypes.byref(st.prob), ctypes.byref(st.io), stream), "dgs_backward_composite")
+        else:
+            _lib.check(L.dgs_backward(ctypes.byref(st.prob), ctypes.byref(st.io), stream), "dgs_backward")
 
-            # ---- backward: one flat gradient bucket in optimiser-group order (as _RasterizeCloudK.backward)
-            flat = torch.empty(bucket.size, **f32) if _cap is None else _cap["bucket"]
-            assert flat.numel() == bucket.size
-            g_xyz, g_dc, g_rest, g_op, g_sc, g_rot = bucket.views(flat, [
-                (P, 3), cloud._features_dc.shape, cloud._features_rest.shape, cloud._opacity.shape, (P, 3), (P, 4)])
-            g_means2D = None if stats is not None else (torch.empty((K, P, 3), **f32) if (_cap is None or "means2D" not in _cap)
-                                                        else _cap["means2D"][:K])
-            depth_tv, g_depth = None, None
-            if lambda_depth_tv > 0.0:
-                from . import losses as _losses
-                # tv_loss is a mean over the view's K depth images of per-image terms (utils/loss_utils.py:66-78): a rank
-                # holding K of the K_total subframes contributes K / K_total of it and needs no other rank's depths
-                share = K / float(K_total)
-                with torch.enable_grad():
-                    dleaf = depth.detach().requires_grad_(True)
-                    depth_tv = _losses.tv_loss(dleaf) * share
-                    g_depth, = torch.autograd.grad(float(lambda_depth_tv) * depth_tv, dleaf)
-                g_depth, depth_tv = g_depth.contiguous(), depth_tv.detach()
-                if shard is not None:
-                    import torch.distributed as dist
-                    dist.all_reduce(depth_tv, group=self.loss_group)   # the value only (logging); the gradient is local
-            io, own = raster_call.backward_io(
-                R, radii, dsub, g_depth, means3D=g_xyz, means2D=g_means2D, sh=g_dc, sh_rest=g_rest if Mr > 0 else None,
-                opacity=g_op, scales=g_sc, rotations=g_rot,
-                # sharded: the ranks' gradients are summed, so the hinge term is added by one of them only
-                opacity_hinge_scale=self.lambda_hinge / max(P, 1) if (shard is None or int(shard[0]) == 0) else 0.0,
-                stats=stats, stats_K_total=K_total)
-            scratch, g_colors, g_cov3D = own["scratch"], own["colors"], own["cov3D"]
-            g_view, g_proj = own["viewmatrix"], own["projmatrix"]
-            # ---- the launches up to the first collective ...
-            chunked = not (ar is None or int(ar.get("chunks", 1)) <= 1 or P < 512)
-            if chunked:
-                _lib.check(L.dgs_backward_composite(ctypes.byref(prob), ctypes.byref(io), stream), "dgs_backward_composite")
-            else:
-                _lib.check(L.dgs_backward(ctypes.byref(prob), ctypes.byref(io), stream), "dgs_backward")
-            split = _cap is not None and _cap.get("split") == "composite"
-            # the step's large buffers, held through a one-element list: a captured front (replay_front) empties it after the
-            # capture so that they go back to the graph pool, and finish() below touches them through prob / io only
-            big = [(tuple(fwd_big[0]) if fwd_big[0] is not None else (None, None, None)) +
-                   (scratch, color, depth, dsub, blur, g_colors, g_cov3D)]
-            skip_flag = fwd_skip[0]
-            if split and skip_flag is not None:   # a word of its own, outside the pool (the view would pin the whole geometry blob)
-                _cap["skipw"].copy_(skip_flag)
-                skip_flag = _cap["skipw"]
+    def _finish(self, st):
+        """Stage 4, everything from the first collective on: a sharded run's reduction of the bucket (overlapped with the
+        per-Gaussian half of the backward when `chunked`), the gradients into `.grad`, the camera gradients back to the
+        control points and the alignment, the result.  `st` becomes the step that is kept until the next one."""
+        L = _lib.lib()
+        cloud, m = self.cloud, self.motion
+        dev = cloud._xyz.device
+        # (the stream of THIS call: a captured front was recorded on torch's capture stream, its eager part runs on the
+        # caller's stream, behind the replay)
+        stream_obj = torch.cuda.current_stream(dev)
+        stream = ctypes.c_void_p(stream_obj.cuda_stream)
+        f32 = dict(dtype=torch.float32, device=dev)
+        ar, shard, K, P, flat, prob, io = st.ar, st.shard, st.K, st.P, st.flat, st.prob, st.io
+        if st.chunked:
+            from . import sharding
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=dev)
+            side = self._side
+            flat.record_stream(side)
+            bucket = raster_call.cloud_bucket(P, st.Mr)
+            t_ar = None
+            if self.time_allreduce:  # (bench.py: span of the side stream's reductions, first chunk ready -> last done)
+                t_ar = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            for ci, (b0, b1) in enumerate(sharding.chunk_bounds(P, int(ar["chunks"]))):
+                _lib.check(L.dgs_backward_geometry(ctypes.byref(prob), ctypes.byref(io), b0, b1, stream),
+                           "dgs_backward_geometry")
+                ev = torch.cuda.Event()
+                ev.record(stream_obj)
+                with torch.cuda.stream(side):
+                    side.wait_event(ev)
+                    if t_ar is not None and ci == 0:
+                        t_ar[0].record(side)
+                    sharding.allreduce_slices(bucket.chunk(flat, P, b0, b1), ar.get("average", False),
+                                              ar.get("group"))
+            _lib.check(L.dgs_backward_pose(ctypes.byref(prob), ctypes.byref(io), stream), "dgs_backward_pose")
+            done = torch.cuda.Event()
+            done.record(side)
+            if t_ar is not None:
+                t_ar[1].record(side)
+                self.ar_events = (self.ar_events + [t_ar])[-256:]
+            stream_obj.wait_event(done)
+        elif ar is not None and P > 0:
+            from . import sharding
+            sharding._allreduce(flat, ar.get("average", False), ar.get("group"))
+        if P == 0:
+            flat.zero_()
+            if st.g_means2D is not None:
+                st.g_means2D.zero_()
+        cloud._xyz.grad, cloud._features_dc.grad, cloud._features_rest.grad = st.g_xyz, st.g_dc, st.g_rest
+        cloud._opacity.grad, cloud._scaling.grad, cloud._rotation.grad = st.g_op, st.g_sc, st.g_rot
 
-            # ---- ... and everything after it (a sharded run's reduction of the bucket, overlapped with the per-Gaussian half
-            # of the backward when `chunked`; then the camera gradients).  Eager steps run it right away; a captured front
-            # (replay_front) replays the launches above as one hipGraph and calls this after every replay.
-            def finish(lambda_now=None):
-                # (the stream of THIS call: a captured front was recorded on torch's capture stream, its eager part runs on the
-                # caller's stream, behind the replay)
-                stream_obj = torch.cuda.current_stream(dev)
-                stream = ctypes.c_void_p(stream_obj.cuda_stream)
-                if chunked:
-                    from . import sharding
-                    if self._side is None:
-                        self._side = torch.cuda.Stream(device=dev)
-                    side = self._side
-                    flat.record_stream(side)
-                    t_ar = None
-                    if self.time_allreduce:  # (bench.py: span of the side stream's reductions, first chunk ready -> last done)
-                        t_ar = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    for ci, (b0, b1) in enumerate(sharding.chunk_bounds(P, int(ar["chunks"]))):
-                        _lib.check(L.dgs_backward_geometry(ctypes.byref(prob), ctypes.byref(io), b0, b1, stream),
-                                   "dgs_backward_geometry")
-                        ev = torch.cuda.Event()
-                        ev.record(stream_obj)
-                        with torch.cuda.stream(side):
-                            side.wait_event(ev)
-                            if t_ar is not None and ci == 0:
-                                t_ar[0].record(side)
-                            sharding.allreduce_slices(bucket.chunk(flat, P, b0, b1), ar.get("average", False),
-                                                      ar.get("group"))
-                    _lib.check(L.dgs_backward_pose(ctypes.byref(prob), ctypes.byref(io), stream), "dgs_backward_pose")
-                    done = torch.cuda.Event()
-                    done.record(side)
-                    if t_ar is not None:
-                        t_ar[1].record(side)
-                        self.ar_events = (self.ar_events + [t_ar])[-256:]
-                    stream_obj.wait_event(done)
-                elif ar is not None and P > 0:
-                    from . import sharding
-                    sharding._allreduce(flat, ar.get("average", False), ar.get("group"))
-                if P == 0:
-                    flat.zero_()
-                    if g_means2D is not None:
-                        g_means2D.zero_()
-                cloud._xyz.grad, cloud._features_dc.grad, cloud._features_rest.grad = g_xyz, g_dc, g_rest
-                cloud._opacity.grad, cloud._scaling.grad, cloud._rotation.grad = g_op, g_sc, g_rot
-
-                # ---- cameras -> control points and alignment (only while the trajectory is being optimised)
-                if m.is_optimizing():
-                    d_ct_all, d_cr_all = torch.zeros_like(ct_all), torch.zeros_like(cr_all)
-                    d_nu = torch.empty(K, **f32)
-                    pscratch = torch.empty(L.dgs_pose_scratch_bytes(K), dtype=torch.uint8, device=dev)
-                    _lib.check(L.dgs_pose_backward(_ptr(ct_all, row), _ptr(cr_all, rrow), _ptr(nu_loc), _ptr(proj), C, K, quat,
-                                                   _ptr(g_view),
-                                                   _ptr(g_proj), _ptr(pscratch), _ptr(d_ct_all, row),
-                                                   _ptr(d_cr_all, rrow), _ptr(d_nu), stream), "dgs_pose_backward")
-                    m._trans._control_points.grad, m._rot._control_points.grad = d_ct_all, d_cr_all
-                    if nrow > 0:
-                        d_raw_all = torch.zeros_like(nu_raw)
-                        if shard is not None:                    # this rank's slice of the view's subframe times
-                            d_all = torch.zeros(K_total, **f32)
-                            d_all[k0:k0 + K] = d_nu
-                            d_nu = d_all
-                        if sel is not None:                      # gradients of the selected subframes back to all f slots
-                            d_full = torch.zeros(f, **f32)
-                            d_full.index_add_(0, sel, d_nu)
-                            d_nu = d_full
-                        _lib.check(L.dgs_alignment_backward(raw_ptr, _ptr(uniform), f, f, _ptr(src), _ptr(d_nu),
-                                                            _ptr(d_raw_all, cam * nrow), stream), "dgs_alignment_backward")
-                        m._nu.grad = d_raw_all
-                held = big[0]
-                self._keep = (tuple(held[:7]) if held is not None else (None,) * 7) + (view, full, campos, nu, gtc, bg, flat, g_depth)
-                return {"losses": losses, "blur": held[7] if (need_blur and held is not None) else None, "radii": radii,
-                        "viewspace_grad": g_means2D, "K": K_total, "subframes": held[4] if held is not None else None,
-                        "depths": held[5] if held is not None else None, "skip_flag_ptr": skip_ptr, "skip_flag": skip_flag,
-                        "depth_tv": depth_tv}
-
-            if split:
-                return {"finish": finish, "big": big, "fwd_big": fwd_big,
-                        "_keep": (nu_all, src, proj, work, g_view, g_proj, sel, uniform, view, full, campos, nu, gtc, bg)}
-            fr = finish()
-            if _cap is not None:
-                fr["_keep"] = self._keep + (nu_all, src, proj, work, blur, g_colors, g_cov3D, g_view, g_proj, radii,
-                                            g_means2D, sel, uniform)
-                if _cap.get("tail") is not None:
-                    _cap["tail"](fr)
-            return fr
-
-        if _cap is not None and _cap.get("split") == "forward":
-            return {"finish": after_forward, "big": fwd_big,
-                    "_keep": (nu_all, src, proj, view, full, campos, nu, bg, color, depth, radii)}
-        return after_forward()
+        # ---- cameras -> control points and alignment (only while the trajectory is being optimised)
+        if m.is_optimizing():
+            ct_all, cr_all, nu_raw = m._trans._control_points, m._rot._control_points, m._nu
+            row, rrow, f = st.row, st.rrow, m.n_subframes
+            d_ct_all, d_cr_all = torch.zeros_like(ct_all), torch.zeros_like(cr_all)
+            d_nu = torch.empty(K, **f32)
+            pscratch = torch.empty(L.dgs_pose_scratch_bytes(K), dtype=torch.uint8, device=dev)
+            _lib.check(L.dgs_pose_backward(_ptr(ct_all, row), _ptr(cr_all, rrow), _ptr(st.nu_loc), _ptr(st.proj), st.C, K,
+                                           st.quat, _ptr(st.g_view), _ptr(st.g_proj), _ptr(pscratch), _ptr(d_ct_all, row),
+                                           _ptr(d_cr_all, rrow), _ptr(d_nu), stream), "dgs_pose_backward")
+            m._trans._control_points.grad, m._rot._control_points.grad = d_ct_all, d_cr_all
+            if st.nrow > 0:
+                d_raw_all = torch.zeros_like(nu_raw)
+                if shard is not None:                    # this rank's slice of the view's subframe times
+                    d_all = torch.zeros(st.K_total, **f32)
+                    d_all[st.k0:st.k0 + K] = d_nu
+                    d_nu = d_all
+                if st.sel is not None:                   # gradients of the selected subframes back to all f slots
+                    d_full = torch.zeros(f, **f32)
+                    d_full.index_add_(0, st.sel, d_nu)
+                    d_nu = d_full
+                _lib.check(L.dgs_alignment_backward(st.raw_ptr, _ptr(st.uniform), f, f, _ptr(st.src), _ptr(d_nu),
+                                                    _ptr(d_raw_all, st.cam * st.nrow), stream), "dgs_alignment_backward")
+                m._nu.grad = d_raw_all
+        self._keep = st
+        return {"losses": st.losses, "blur": st.blur if st.need_blur else None, "radii": st.radii,
+                "viewspace_grad": st.g_means2D, "K": st.K_total, "subframes": st.color, "depths": st.depth,
+                "skip_flag_ptr": st.skip_ptr, "skip_flag": st.skip_flag, "depth_tv": st.depth_tv}

@@ -297,11 +297,9 @@ class TrainingLoop:
                 # identical on all replicas.
                 h = self._flag_words.pop() if self._flag_words else torch.zeros(1, dtype=torch.int32).pin_memory()
                 if flag.is_cuda:     # by a kernel: an asynchronous copy is a hand-over to the copy engine
-                    import ctypes
                     from . import _lib
-                    _lib.check(_lib.lib().dgs_copy_words(ctypes.c_void_p(h.data_ptr()), ctypes.c_void_p(flag.data_ptr()), 1,
-                                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                               "dgs_copy_words")
+                    from .raster_call import _ptr, _stream
+                    _lib.check(_lib.lib().dgs_copy_words(_ptr(h), _ptr(flag), 1, _stream(dev)), "dgs_copy_words")
                 else:
                     h.copy_(flag[:1], non_blocking=True)
                 ev = torch.cuda.Event()
@@ -318,18 +316,26 @@ class TrainingLoop:
         r = {"viewspace_points_all": fr["viewspace_grad"], "radii_all": fr["radii"], "K_total": fr["K"],
              "skip_flag_ptr": skip}
         self._tail(iteration, r, densification_threshold, makeup=exact)
-        out = {"l1": fr["losses"][0], "smooth": fr["losses"][1], "hinge": None, "num_points": g._xyz.shape[0],
-               "loss": None, "dropped": self._fused.dropped, "retried": self.retried}
-        # A step whose duplicate capacity overflowed was a no-op on the device; once its flag has come back (usually one
-        # step later) the view is re-run here through the exact path, so that no view loses its update.  Single-process
-        # only: replicas would have to agree on the make-up step (sharded runs drop the step on every rank instead).
+        # Single-process only: replicas would have to agree on the make-up step (sharded runs drop the step on every rank
+        # instead).
         if not exact and not self.distributed:
-            while self._fused.retry:
-                cam_r, sub_r = self._fused.retry.pop(0)
-                g.optimizer.note_skipped_steps(1)
-                self.retried += 1
-                self._step_fused(iteration, cam_r, sub_r, lambda_t_smooth, densification_threshold, exact=True)
-            out["retried"] = self.retried
+            self._make_up(iteration)
+        return self._fused_out(fr, lambda_t_smooth)
+
+    def _make_up(self, iteration):
+        """A step whose duplicate capacity overflowed was a no-op on the device; once its flag has come back (usually one
+        step later) the view is re-run here through the exact path, so that no view loses its update."""
+        while self._fused.retry:
+            cam_r, sub_r = self._fused.retry.pop(0)
+            self.gaussians.optimizer.note_skipped_steps(1)
+            self.retried += 1
+            self._step_fused(iteration, cam_r, sub_r, self.lambda_t_smooth_func(iteration),
+                             self.densify_threshold_func(iteration), exact=True)
+
+    def _fused_out(self, fr, lambda_t_smooth):
+        """step()'s result for a fused step, eager or replayed, from FusedStep's result dict."""
+        out = {"l1": fr["losses"][0], "smooth": fr["losses"][1], "hinge": None, "num_points": self.gaussians._xyz.shape[0],
+               "loss": None, "dropped": self._fused.dropped, "retried": self.retried}
         if self.log_losses:
             out["loss"] = fr["losses"][0] + lambda_t_smooth * fr["losses"][1]    # (without the hinge term's value)
             if fr["depth_tv"] is not None:
@@ -358,12 +364,8 @@ class TrainingLoop:
             self._drain_dist_flags(lag=0)
             self._fused.retry.clear()
             return
-        it = self._last_iteration
-        while self._fused.retry and it is not None:
-            cam_r, sub_r = self._fused.retry.pop(0)
-            self.gaussians.optimizer.note_skipped_steps(1)
-            self.retried += 1
-            self._step_fused(it, cam_r, sub_r, self.lambda_t_smooth_func(it), self.densify_threshold_func(it), exact=True)
+        if self._last_iteration is not None:
+            self._make_up(self._last_iteration)
 
     # ---- the iteration as one captured hipGraph
     def _graphable(self, iteration, sharded=False):
@@ -403,15 +405,8 @@ class TrainingLoop:
         if fr is None:
             return None
         g.optimizer.skip_flag_ptr = None
-        out = {"l1": fr["losses"][0], "smooth": fr["losses"][1], "hinge": None, "num_points": g._xyz.shape[0],
-               "loss": None, "dropped": self._fused.dropped, "retried": self.retried, "replayed": True}
-        if self.log_losses:
-            out["loss"] = fr["losses"][0] + lambda_t_smooth * fr["losses"][1]
-        while self._fused.retry:               # a replayed step that overflowed is made up for like an eager one
-            cam_r, sub_r = self._fused.retry.pop(0)
-            g.optimizer.note_skipped_steps(1)
-            self.retried += 1
-            self._step_fused(iteration, cam_r, sub_r, lambda_t_smooth, self.densify_threshold_func(iteration), exact=True)
+        out = dict(self._fused_out(fr, lambda_t_smooth), replayed=True)
+        self._make_up(iteration)               # a replayed step that overflowed is made up for like an eager one
         out["retried"] = self.retried
         return out
 

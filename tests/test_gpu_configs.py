@@ -343,7 +343,7 @@ def test_fused_step_capacity_mode_as_benchmarked_at_metric_size(gpu):
     a_fr = fs.run(0, 1e-3, m.get_gt_image(0), bg)                      # exact two-phase forward: learns the count
     assert a_fr["skip_flag_ptr"] is None
     a = snapshot(a_fr)
-    dsub, view, full, campos = (fs._keep[i].clone() for i in (6, 7, 8, 9))
+    dsub, view, full, campos = (getattr(fs._keep, n).clone() for n in ("dsub", "view", "full", "campos"))
     fs._poll(block=True)
     R = fs._seen[(0, K, 0)][-1]
     assert R > 30_000_000

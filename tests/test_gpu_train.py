@@ -1045,6 +1045,52 @@ def test_sharded_step_falls_back_only_when_the_capture_itself_is_refused(gpu):
         dist.destroy_process_group()
 
 
+@pytest.mark.parametrize("family", ["replay", "front"])
+def test_captured_steps_give_their_large_buffers_back_to_the_pool(gpu, family):
+    """All captured steps share one memory pool that holds ONE step's buffers: a capture hands its step's large buffers
+    (fused_step._Step.LARGE) back when it is done, and the next view's capture re-uses the blocks.  A capture that kept
+    them would hold the subframe stack, dL/dsubframes and the three state blobs per captured view (the soak run in
+    FusedStep.invalidate's comment: 159 GiB instead of 25).  So the memory in use right after a replayed step grows from
+    two captured views to three by less than one subframe stack, K * 3 * H * W * 4 bytes -- only the few small per-graph
+    tensors outside the pool are added.  family: the single-process step (FusedStep.replay) and the sharded front
+    (replay_front, a one-rank gloo "views" group with the default ar_chunks)."""
+    import socket
+    import torch
+    import torch.distributed as dist
+    from deblurgs_amd.training import TrainingLoop, default_optimization_params
+    K, H, W = 5, 96, 144
+    opt = default_optimization_params(iterations=10 ** 6, curve_start_iter=1, densify_from_iter=10 ** 9,
+                                      densify_until_iter=0, opacity_reset_interval=10 ** 9)
+    if family == "front":
+        with socket.socket() as sock:
+            sock.bind(("127.0.0.1", 0))
+            port = sock.getsockname()[1]
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    try:
+        sc, cloud, m = _fused_fixture(K=K, P=3000)
+        assert (sc["H"], sc["W"]) == (H, W)
+        loop = TrainingLoop(cloud, m, opt, cameras_extent=1.0, graph="always",
+                            distributed="views" if family == "front" else False)
+        fs = loop._fused
+        in_use = {}
+        for it in range(1, 31):
+            replayed = fs.replayed
+            loop.step(it, it % 3)
+            if fs.replayed > replayed and fs.captured in (2, 3) and fs.captured not in in_use:
+                torch.cuda.synchronize()
+                in_use[fs.captured] = torch.cuda.memory_allocated()
+            if len(in_use) == 2:
+                break
+        assert sorted(in_use) == [2, 3], (in_use, fs.captured, fs.replayed)
+        grew = in_use[3] - in_use[2]
+        print(f"\n[{family}] in use after a replayed step: {in_use[2]} B with two captured views, {in_use[3]} B with three "
+              f"(+{grew} B; one subframe stack is {K * 3 * H * W * 4} B)")
+        assert grew < K * 3 * H * W * 4
+    finally:
+        if family == "front":
+            dist.destroy_process_group()
+
+
 # The N-rank code path end to end with two ranks sharing this box's GPU (gloo collectives staged through the host: a
 # functional check, not a measurement; RCCL itself needs the driver's multi-GPU run).  One test per leg, so that one leg
 # going red names itself and hides nothing else (VERDICT r3, weak 3).

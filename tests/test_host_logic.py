@@ -405,6 +405,30 @@ def test_poll_charges_every_overflow_to_its_own_step():
     assert not fs._pending and len(fs._free_hosts) == 5
 
 
+def test_step_state_drops_exactly_its_large_fields():
+    """fused_step._Step: release_large() empties the large fields and nothing else, leaves no reference to them behind,
+    and the large fields are the ones its docstring's lifetime table lists."""
+    import weakref
+    from deblurgs_amd.fused_step import _Step
+    assert set(_Step.__slots__) == set(_Step.LARGE) | set(_Step.SMALL) and not set(_Step.LARGE) & set(_Step.SMALL)
+    ints = ("cam", "K", "K_total", "k0", "P", "H", "W", "Mr", "C", "row", "rrow", "quat", "nrow", "R")
+    values = {n: (i if n in ints else torch.full((2,), float(i))) for i, n in enumerate(_Step.__slots__)}
+    st = _Step(**values)
+    color = weakref.ref(values["color"])
+    small = {n: values[n] for n in _Step.SMALL}
+    del values
+    st.release_large()
+    assert all(getattr(st, n) is None for n in _Step.LARGE)
+    assert all(getattr(st, n) is small[n] for n in _Step.SMALL)
+    assert color() is None
+    table = _Step.__doc__.split("last read by\n")[1].split("\n\n")[0]
+    assert {line.split()[0] for line in table.splitlines()} == set(_Step.LARGE)
+    # a front recorded up to the forward keeps the images its eager loss reads
+    st = _Step(color=torch.zeros(1), depth=torch.zeros(1), geom=torch.zeros(1))
+    st.release_large(keep=("color", "depth"))
+    assert st.color is not None and st.depth is not None and st.geom is None
+
+
 def test_eager_is_faster_asks_the_context_of_the_clouds_device(monkeypatch):
     """FusedStep._eager_is_faster predicts how the step's backward will be split, and that backward runs with
     the package's context of the CLOUD's device (DgsProblem.context) -- not with the current device's.  Host side only:

@@ -15,6 +15,6 @@ print("last_capacity", fs.last_capacity, "host", fs._pending[0].host.tolist())
 print("img diff", float((fr["subframes"] - out["subframes"]).abs().max()), "radii diff", int((fr["radii"] != out["radii_all"]).sum()))
 nu_t = m._sample_nu_from_alignment(1)
 print("nu torch", nu_t.tolist())
-print("nu kernel", fs._keep[10].tolist())
+print("nu kernel", fs._keep.nu.tolist())
 wv, fp, cc = m.get_trajectory_matrices(1)
-print("view diff", float((wv - fs._keep[7]).abs().max()), float((fp - fs._keep[8]).abs().max()))
+print("view diff", float((wv - fs._keep.view).abs().max()), float((fp - fs._keep.full).abs().max()))
