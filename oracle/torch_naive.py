@@ -124,7 +124,7 @@ def preprocess(means3D, opacities, viewmatrix, projmatrix, campos, W, H, tanfovx
         raw = eval_sh_color(sh_degree, sh, d)
         color = torch.sigmoid(raw) if use_sigmoid else torch.clamp(raw + 0.5, min=0.0)
     return dict(depth=depth, pix=pix, conic=conic, opacity=opacities.reshape(-1), color=color, radius=radius,
-                rect=(minx, miny, maxx, maxy), visible=visible)
+                rect=(minx, miny, maxx, maxy), visible=visible, p_view=p_view)
 
 
 def rasterize(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, tanfovx, tanfovy, z_far=100.0,
