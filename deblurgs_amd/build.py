@@ -46,6 +46,8 @@ SOURCES = {
     "scene.hip": ["-ffp-contract=off"],
     # PNG row filters, deflate and checksums: integers only
     "png.hip": [],
+    # JPEG colour conversion, transform, quantiser and Huffman coding: integers only
+    "jpeg.hip": [],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -7,11 +7,13 @@ after every training) on the batched forward-only rasteriser, with the 8-bit fra
                       group g - 1 while group g is enqueued.  One stream, a linear chain, no graph.
     render_spiral     get_render_path (utils/export_utils.py:86-152) + render_spiral.py:27-33
     render_trainview  render_trainview.py:23-52: the middle camera of every training trajectory beside its ground truth
-    write_frames      PNG files through PIL when it is importable, else one .npy; encoding a video is the caller's
-                      (imageio is no dependency of this package): render_spiral / render_trainview take a
-                      writer(frames, path, fps) callable.
+    write_frames      PNG files through PIL when it is importable, else one .npy.  render_spiral / render_trainview take a
+                      writer(frames, path, fps) callable for the video: deblurgs_amd.video.make_video is one (a
+                      Motion-JPEG AVI, the frames encoded on the device); imageio is no dependency of this package.
     write_frames_png  render_frames' loop with the PNG files made on the device (deblurgs_amd/png.py): the finished bytes
                       cross to the host, not the raw frames.  Opt-in; needs no PIL.
+    write_frames_video  the same loop with JPEG files made on the device (deblurgs_amd/jpeg.py) appended to one
+                      Motion-JPEG AVI (deblurgs_amd/video.py).  Opt-in.
 
 Path geometry is the reference's, in float64 numpy: mean_camera_pose / c2w_from_eye (utils/mvg_utils.py:56-98),
 cam_to_c2w / c2w_to_cam (scene/cameras.py:77-120), center_crop_window (center_crop_with_ratio's int() arithmetic), all
@@ -362,7 +364,8 @@ def render_frames(cams, cloud, bg, tone_mapping=None, crop_ratio=1.0, frames_per
 def render_spiral(motion, cloud, bg, tone_mapping=None, spin_angle=5.0, n_frames=50, spin_for=2, crop_ratio=1.0,
                   frames_per_call=None, depth=False, writer=None, path=None, fps=32):
     """render_spiral.py:23-35: the frames of spiral_path(motion, cloud, ...) -- what render_frames returns.  writer: a
-    callable writer(frames, path, fps) that encodes them (the reference's make_video); none is bundled."""
+    callable writer(frames, path, fps) that encodes them (the reference's make_video; deblurgs_amd.video.make_video
+    writes a Motion-JPEG AVI).  writer=None writes nothing."""
     cams = spiral_path(motion, cloud, spin_angle=spin_angle, n_frames=n_frames, spin_for=spin_for)
     out = render_frames(cams, cloud, bg, tone_mapping, crop_ratio=crop_ratio, frames_per_call=frames_per_call, depth=depth)
     if writer is not None:
@@ -459,6 +462,74 @@ def write_frames_png(cams, cloud, bg, directory, tone_mapping=None, crop_ratio=1
         if job is not None:
             write(job)
     return paths
+
+
+@torch.no_grad()
+def write_frames_video(cams, cloud, bg, path, fps, tone_mapping=None, crop_ratio=1.0, frames_per_call=None, quality=90,
+                       subsampling="4:2:0"):
+    """write_frames_png's three-stage loop with the frames made into JPEG files on the device (deblurgs_amd/jpeg.py) and
+    appended to ONE Motion-JPEG AVI (deblurgs_amd/video.py): while group g is rendered and encoded, the bytes of group g - 1
+    are copied (sizes first: that many bytes, not the slot) and the frames of group g - 2 are appended to the file.  The
+    frames are jpeg.to_bytes(render_frames(...)) byte for byte; returns the path."""
+    from . import jpeg, video
+    cams = list(cams)
+    if not cams:
+        raise ValueError("no cameras")
+    groups = frame_groups(cams, FRAMES_PER_CALL if frames_per_call is None else frames_per_call)
+    H, W = int(cams[0].image_height), int(cams[0].image_width)
+    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
+        raise ValueError("write_frames_video: the cameras must share one image size")
+    window = center_crop_window(H, W, crop_ratio)
+    h, w = window[1] - window[0], window[3] - window[2]
+    if h < 1 or w < 1:
+        raise ValueError(f"crop_ratio {crop_ratio} leaves no pixel of a {W} x {H} image")
+    if cams[0].world_view_transform.device.type != "cuda":
+        raise RuntimeError("write_frames_video needs cameras and a cloud on a HIP device (no CPU fallback)")
+    G = max(e - b for b, e in groups)
+    # (the bound is the worst case of noise at quality 100; the pinned buffers grow to what the frames really take)
+    pinned = [torch.empty(1 << 16, dtype=torch.uint8).pin_memory() for _ in range(2)]
+    pinned_sizes = [torch.empty(G, dtype=torch.int64).pin_memory() for _ in range(2)]
+
+    def copy_bytes(job):        # stage 2: the sizes are on the host; enqueue a copy of that many bytes per file
+        job["sized"].synchronize()
+        job["sizes"] = pinned_sizes[job["slot"]][:job["count"]].tolist()
+        if pinned[job["slot"]].numel() < sum(job["sizes"]):
+            pinned[job["slot"]] = torch.empty(2 * sum(job["sizes"]), dtype=torch.uint8).pin_memory()
+        at = 0
+        for k, size in enumerate(job["sizes"]):
+            pinned[job["slot"]][at:at + size].copy_(job["files"][k, :size], non_blocking=True)
+            at += size
+        job["copied"] = torch.cuda.Event()
+        job["copied"].record()
+
+    with video.MjpegAviWriter(path, fps, quality, subsampling) as out:
+        def write(job):         # stage 3
+            job["copied"].synchronize()
+            host, at = pinned[job["slot"]].numpy(), 0
+            for size in job["sizes"]:
+                out._add(host[at:at + size].tobytes(), (w, h))
+                at += size
+
+        jobs = []
+        for g, (b, e) in enumerate(groups):
+            files, sizes = jpeg.encode(frames_finish(render_group(cams[b:e], cloud, bg)["render"], tone_mapping, window),
+                                       quality, subsampling)
+            job = {"slot": g % 2, "count": e - b, "files": files, "sized": torch.cuda.Event()}
+            pinned_sizes[job["slot"]][:e - b].copy_(sizes.view(torch.int64), non_blocking=True)
+            job["sized"].record()
+            jobs.append(job)
+            if g >= 2:
+                write(jobs[g - 2])
+                jobs[g - 2] = None
+            if g >= 1:
+                copy_bytes(jobs[g - 1])
+        for job in jobs[-2:]:
+            if job is not None and "copied" not in job:
+                copy_bytes(job)
+        for job in jobs[-2:]:
+            if job is not None:
+                write(job)
+    return path
 
 
 def write_frames(frames, directory):

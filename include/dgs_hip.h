@@ -944,6 +944,42 @@ size_t dgs_png_tmp_bytes(int32_t n, int32_t w, int32_t h, int32_t channels);
 int dgs_png_encode(const uint8_t* images, int32_t n, int32_t w, int32_t h, int32_t channels, size_t image_stride,
                    uint8_t* files, size_t file_stride, uint64_t* sizes, void* tmp, dgs_stream_t stream);
 
+/* ---- JPEG files made on the device (additions to ABI 15) ----
+ * dgs_jpeg_encode: n 8-bit images -> n finished baseline JFIF files (the frames of a Motion-JPEG AVI, deblurgs_amd/video.py,
+ * or lone .jpg files).  The calling rules are dgs_png_encode's: image i is h w channels contiguous bytes at images +
+ * i image_stride, file i starts at files + i file_stride (file_stride >= dgs_jpeg_bound, any alignment), sizes[i] (a device
+ * uint64, 8-byte aligned) is its length and the bytes of the slot past it are not written; tmp is dgs_jpeg_tmp_bytes bytes of
+ * the caller's, any alignment; nothing is allocated, no host synchronisation, nothing kept between calls: capturable.  Two
+ * launches.  channels 1 is gray (subsampling is ignored, the MCU is one block), 3 is RGB; subsampling DGS_JPEG_444 or
+ * DGS_JPEG_420; quality 1..100; w, h 1..65535.
+ * The bytes are a function of the pixels, in integers (arithmetic shifts, everything fits int32):
+ *   colour     Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *              Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16, Cb and Cr clipped to 0..255; gray: Y = the byte
+ *   padding    to a multiple of the MCU (8; 16 at 4:2:0) by repeating the last column, then the last row, at full resolution
+ *   4:2:0      Cb, Cr = (a + b + c + d + 2) >> 2 over each 2 x 2
+ *   transform  samples - 128; M[u][x] = rint(8192 c(u) / 2 cos((2x + 1) u pi / 16)), c(0) = sqrt(1/2), c(u) = 1 otherwise;
+ *              t[y][u] = (sum_x M[u][x] b[y][x] + 512) >> 10, F[v][u] = (sum_y M[v][y] t[y][u] + 4096) >> 13: 8 x the coefficient
+ *   quantiser  Annex K.1 / K.2 base tables, s = 5000 / quality below 50, else 200 - 2 quality, q = clip((base s + 50) / 100,
+ *              1, 255), level = sign(F) ((|F| + 4 q) / (8 q))  (integer divisions)
+ *   entropy    baseline sequential, the Annex K.3 - K.6 Huffman tables, zig-zag order, ZRL for runs above 15, EOB unless
+ *              coefficient 63 is non-zero; the restart interval is one MCU row: its bits start on a byte with DC predictors 0
+ *              and are padded with 1-bits, every 0xFF is followed by 0x00, row r (all but the last) by RST(r & 7)
+ *   file       SOI, APP0 "JFIF" 1.01 (no units, density 1:1), one DQT (both tables, zig-zag order; one for gray), SOF0
+ *              (component ids 1, 2, 3, luma sampling 0x22 or 0x11, table selectors 0, 1, 1), four DHT (luma DC, luma AC, chroma
+ *              DC, chroma AC; two for gray), DRI = MCUs per row, SOS, the scan, EOI
+ * dgs_jpeg_bound = 625 (334 gray) + 416 blocks + 2 MCU rows + 2: the header; per 8 x 8 block the longest code sequence
+ * (22 + 63 * 26 = 1660 bits, 208 bytes) doubled for stuffing; an RST marker per MCU row; EOI.  0 for arguments the call
+ * refuses.  n = 0 succeeds without a launch.  Refused before anything is enqueued: channels other than 1 and 3, w or h
+ * outside 1..65535, another subsampling, a quality outside 1..100, a negative n, a NULL pointer, an image_stride below
+ * h w channels, a file_stride below the bound, a misaligned sizes, more than 2^31 - 1 blocks. */
+#define DGS_JPEG_444 0
+#define DGS_JPEG_420 1
+size_t dgs_jpeg_bound(int32_t w, int32_t h, int32_t channels, int32_t subsampling);
+size_t dgs_jpeg_tmp_bytes(int32_t n, int32_t w, int32_t h, int32_t channels, int32_t subsampling);
+int dgs_jpeg_encode(const uint8_t* images, int32_t n, int32_t w, int32_t h, int32_t channels, size_t image_stride,
+                    int32_t quality, int32_t subsampling, uint8_t* files, size_t file_stride, uint64_t* sizes, void* tmp,
+                    dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
