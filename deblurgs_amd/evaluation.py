@@ -659,10 +659,9 @@ def evaluate(cams, cloud, bg, gt_images, tone_mapping, views_per_call=None, vis_
         tone_mapping = losses.ToneMapping(tone_mapping or "identity")
     if writer is not None and vis_dir is None:
         raise ValueError("writer takes the place of the files under vis_dir: give vis_dir too (it names the paths)")
-    if device_png and writer is not None:
-        raise ValueError("device_png writes the files itself: it cannot be combined with a writer")
+    from . import report
+    report.no_writer_with_device_png(writer, device_png)
     if vis_dir is not None and writer is None:
-        from . import report
         report.fresh_directory(vis_dir)
     if views_per_call is not None:
         return _evaluate_grouped(cams, cloud, bg, gt_images, tone_mapping, views_per_call, vis_dir, writer, lpips,

@@ -5,7 +5,8 @@
                                .jpg (its own quantisation and Huffman tables, one restart interval per MCU row).  No host
                                pass over the bytes, no synchronisation.
     to_bytes(images, ...)      the files as a list of bytes: one read of the sizes, then a copy of sizes[i] bytes each.
-    write_files(images, paths, ...)   to_bytes, written.
+    write_files(images, paths, ...)   to_bytes, written.  (All three are thin: the tensor checks, the buffers and the
+                               download are deblurgs_amd/device_files.py's, shared with png.py.)
     segments(data)             a small HOST parser of a JPEG byte string: (marker, payload) per segment, the entropy-coded
                                bytes as the payload of the SOS entry's successor (tests, tools).
 
@@ -14,10 +15,7 @@ tables the way libjpeg does.  Colour conversion, the 8 x 8 transform and the qua
 include/dgs_hip.h: the bytes are a function of the pixels (tests/jpeg_cases.py restates them in numpy).  Opt-in: video.py
 wraps the files into a Motion-JPEG AVI, render_path.write_frames_video writes a camera path.
 """
-import torch
-
-from . import _lib
-from .raster_call import _ptr, _stream
+from . import _lib, device_files
 
 SUBSAMPLING = {"4:4:4": 0, "4:2:0": 1}      # DGS_JPEG_444, DGS_JPEG_420
 SOI, EOI, SOS = 0xD8, 0xD9, 0xDA
@@ -39,58 +37,29 @@ def bound(w, h, c, subsampling="4:2:0"):
     return b
 
 
-def _as_nhwc(images):
-    if images.device.type != "cuda":
-        raise RuntimeError("jpeg.encode needs a tensor on a HIP device (no CPU fallback)")
-    if images.dtype != torch.uint8 or images.dim() not in (3, 4):
-        raise ValueError("jpeg.encode takes a uint8 [n,h,w,3], [n,h,w,1] or [n,h,w] tensor")
-    if images.dim() == 3:
-        images = images[..., None]
-    if images.shape[3] not in (1, 3):
-        raise ValueError(f"jpeg.encode takes 1 (gray) or 3 (RGB) channels, not {int(images.shape[3])}")
-    return images.contiguous()
-
-
 def encode(images, quality=90, subsampling="4:2:0", files=None):
     """(files [n,stride] uint8, sizes [n] uint64) on the device; stride >= bound(w, h, c, subsampling).  files: a uint8
     device tensor [n,stride] to write into (e.g. a reused buffer); bytes of a row past sizes[i] are left as they are."""
-    images = _as_nhwc(images)
+    images = device_files.as_nhwc(images, "jpeg.encode", "[n,h,w,3], [n,h,w,1] or [n,h,w]", (1, 3))
     sub = _subsampling(subsampling)
     quality = int(quality)
     if not 1 <= quality <= 100:
         raise ValueError(f"quality must be 1..100 (got {quality})")
     n, h, w, c = (int(s) for s in images.shape)
     L = _lib.lib()
-    need = bound(w, h, c, subsampling)
-    if files is None:
-        files = torch.empty((n, (need + 15) // 16 * 16), dtype=torch.uint8, device=images.device)
-    elif (files.dtype != torch.uint8 or files.dim() != 2 or files.shape[0] != n or files.shape[1] < need or
-          files.device != images.device or files.stride(1) != 1):
-        raise ValueError(f"files must be a uint8 [n, >= {need}] tensor on the images' device")
-    sizes = torch.empty(n, dtype=torch.uint64, device=images.device)
-    tmp = torch.empty(max(L.dgs_jpeg_tmp_bytes(n, w, h, c, sub), 16), dtype=torch.uint8, device=images.device)
-    _lib.check(L.dgs_jpeg_encode(_ptr(images), n, w, h, c, h * w * c, quality, sub, _ptr(files),
-                                 max(int(files.stride(0)), int(files.shape[1])), _ptr(sizes), _ptr(tmp),
-                                 _stream(images.device)), "dgs_jpeg_encode")
-    return files, sizes
+    return device_files.encode(
+        images, bound(w, h, c, subsampling), L.dgs_jpeg_tmp_bytes(n, w, h, c, sub), files,
+        lambda src, *out: L.dgs_jpeg_encode(src, n, w, h, c, h * w * c, quality, sub, *out), "dgs_jpeg_encode")
 
 
 def to_bytes(images, quality=90, subsampling="4:2:0"):
     """The n files as a list of bytes (one host read of the sizes, then sizes[i] bytes of each file)."""
-    files, sizes = encode(images, quality, subsampling)
-    host_sizes = sizes.view(torch.int64).cpu().tolist()
-    return [files[i, :s].cpu().numpy().tobytes() for i, s in enumerate(host_sizes)]
+    return device_files.download(*encode(images, quality, subsampling))
 
 
 def write_files(images, paths, quality=90, subsampling="4:2:0"):
     """images [n,...] -> the n files named by paths.  Returns the paths."""
-    paths = list(paths)
-    if len(paths) != int(images.shape[0]):
-        raise ValueError("one path per image")
-    for path, data in zip(paths, to_bytes(images, quality, subsampling)):
-        with open(path, "wb") as f:
-            f.write(data)
-    return paths
+    return device_files.write_files(images, paths, lambda images: to_bytes(images, quality, subsampling))
 
 
 def segments(data):

@@ -4,7 +4,8 @@
                                on the device: file i is files[i, :sizes[i]], a complete .png (signature, IHDR, one IDAT,
                                IEND, every CRC).  No host pass over the bytes, no synchronisation.
     to_bytes(images)           the files as a list of bytes: one read of the sizes, then a copy of sizes[i] bytes each.
-    write_files(images, paths) to_bytes, written.
+    write_files(images, paths) to_bytes, written.  (All three are thin: the tensor checks, the buffers and the download are
+                               deblurgs_amd/device_files.py's, shared with jpeg.py.)
     chunks(data)               a small HOST parser of a PNG byte string: (type, payload, crc_ok) per chunk (tests, tools).
 
 c = 1 / 2 / 3 / 4 is gray / gray + alpha / RGB / RGBA.  Row filters by the smallest sum of |residual as int8|, deflate in
@@ -15,10 +16,7 @@ traj_render / evaluation.evaluate take device_png=True, render_path.write_frames
 import struct
 import zlib
 
-import torch
-
-from . import _lib
-from .raster_call import _ptr, _stream
+from . import _lib, device_files
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 COLOR_TYPE = {1: 0, 2: 4, 3: 2, 4: 6}      # channels -> IHDR colour type
@@ -32,51 +30,25 @@ def bound(w, h, c):
     return b
 
 
-def _as_nhwc(images):
-    if images.device.type != "cuda":
-        raise RuntimeError("png.encode needs a tensor on a HIP device (no CPU fallback)")
-    if images.dtype != torch.uint8 or images.dim() not in (3, 4):
-        raise ValueError("png.encode takes a uint8 [n,h,w,c] or [n,h,w] tensor")
-    if images.dim() == 3:
-        images = images[..., None]
-    return images.contiguous()
-
-
 def encode(images, files=None):
     """(files [n,stride] uint8, sizes [n] uint64) on the device; stride >= bound(w, h, c).  files: a uint8 device tensor
     [n,stride] to write into (e.g. a reused buffer); bytes of a row past sizes[i] are left as they are."""
-    images = _as_nhwc(images)
+    images = device_files.as_nhwc(images, "png.encode", "[n,h,w,c] or [n,h,w]", COLOR_TYPE)
     n, h, w, c = (int(s) for s in images.shape)
     L = _lib.lib()
-    need = bound(w, h, c)
-    if files is None:
-        files = torch.empty((n, (need + 15) // 16 * 16), dtype=torch.uint8, device=images.device)
-    elif (files.dtype != torch.uint8 or files.dim() != 2 or files.shape[0] != n or files.shape[1] < need or
-          files.device != images.device or files.stride(1) != 1):
-        raise ValueError(f"files must be a uint8 [n, >= {need}] tensor on the images' device")
-    sizes = torch.empty(n, dtype=torch.uint64, device=images.device)
-    tmp = torch.empty(max(L.dgs_png_tmp_bytes(n, w, h, c), 16), dtype=torch.uint8, device=images.device)
-    _lib.check(L.dgs_png_encode(_ptr(images), n, w, h, c, h * w * c, _ptr(files), max(int(files.stride(0)), int(files.shape[1])),
-                                _ptr(sizes), _ptr(tmp), _stream(images.device)), "dgs_png_encode")
-    return files, sizes
+    return device_files.encode(
+        images, bound(w, h, c), L.dgs_png_tmp_bytes(n, w, h, c), files,
+        lambda src, *out: L.dgs_png_encode(src, n, w, h, c, h * w * c, *out), "dgs_png_encode")
 
 
 def to_bytes(images):
     """The n files as a list of bytes (one host read of the sizes, then sizes[i] bytes of each file)."""
-    files, sizes = encode(images)
-    host_sizes = sizes.view(torch.int64).cpu().tolist()
-    return [files[i, :s].cpu().numpy().tobytes() for i, s in enumerate(host_sizes)]
+    return device_files.download(*encode(images))
 
 
 def write_files(images, paths):
     """images [n,...] -> the n files named by paths.  Returns the paths."""
-    paths = list(paths)
-    if len(paths) != int(images.shape[0]):
-        raise ValueError("one path per image")
-    for path, data in zip(paths, to_bytes(images)):
-        with open(path, "wb") as f:
-            f.write(data)
-    return paths
+    return device_files.write_files(images, paths, to_bytes)
 
 
 def chunks(data):

@@ -14,6 +14,9 @@ after every training) on the batched forward-only rasteriser, with the 8-bit fra
                       cross to the host, not the raw frames.  Opt-in; needs no PIL.
     write_frames_video  the same loop with JPEG files made on the device (deblurgs_amd/jpeg.py) appended to one
                       Motion-JPEG AVI (deblurgs_amd/video.py).  Opt-in.
+                      All three start from one _path_plan (the cameras' groups, the shared image size, the crop window);
+                      the two that make files are one _path_files pipeline -- render + encode group g, copy the bytes of
+                      g - 1, write g - 2, over two device_files.Download slots -- with their own encode and sink.
 
 Path geometry is the reference's, in float64 numpy: mean_camera_pose / c2w_from_eye (utils/mvg_utils.py:56-98),
 cam_to_c2w / c2w_to_cam (scene/cameras.py:77-120), center_crop_window (center_crop_with_ratio's int() arithmetic), all
@@ -21,13 +24,14 @@ pinned by tests/golden/paths_golden.npz.  depth_colorize (utils/export_utils.py:
 clip_percentage = 1 (dgs_depth_range + dgs_depth_colorize); its jet_r table is built here from the published segment
 definition of "jet" (matplotlib need not be installed) and pinned by the same fixture.
 """
+import collections
 import math
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, gaussian_renderer, losses
+from . import _lib, device_files, gaussian_renderer, losses
 from .pose import MiniCam, get_projection_matrix
 from .raster_call import _ptr, _stream
 
@@ -289,6 +293,30 @@ def render_group(cams, cloud, bg):
         return gaussian_renderer.render_subframes(wv, fp, cc, cams[0], cloud, bg)
 
 
+_PathPlan = collections.namedtuple("_PathPlan", "cams groups H W window h w device G")
+
+
+def _path_plan(cams, crop_ratio, frames_per_call, who):
+    """What every loop over a camera path starts from: the cameras as a list, their frame_groups, the one image size H, W
+    they share, the crop window and its size h, w, their device, and G, the cameras of the largest group.  who: the
+    caller's name for the messages."""
+    cams = list(cams)
+    if not cams:
+        raise ValueError("no cameras")
+    groups = frame_groups(cams, FRAMES_PER_CALL if frames_per_call is None else frames_per_call)
+    H, W = int(cams[0].image_height), int(cams[0].image_width)
+    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
+        raise ValueError(f"{who} makes one array, one directory or one video: the cameras must share one image size")
+    window = center_crop_window(H, W, crop_ratio)
+    h, w = window[1] - window[0], window[3] - window[2]
+    if h < 1 or w < 1:
+        raise ValueError(f"crop_ratio {crop_ratio} leaves no pixel of a {W} x {H} image")
+    device = cams[0].world_view_transform.device
+    if device.type != "cuda":
+        raise RuntimeError(f"{who} needs cameras and a cloud on a HIP device (no CPU fallback)")
+    return _PathPlan(cams, groups, H, W, window, h, w, device, max(e - b for b, e in groups))
+
+
 class _HostRing:
     """Two pinned host buffers and their events: group g's bytes are copied into buffer g % 2 on the rendering stream,
     and drained into the result while group g + 1 is enqueued."""
@@ -324,22 +352,8 @@ def render_frames(cams, cloud, bg, tone_mapping=None, crop_ratio=1.0, frames_per
     the depth images stay on the device, 4 H W bytes per frame, until the last group is rendered, and are coloured in a
     second pass).  Cameras are rendered frames_per_call at a time (default FRAMES_PER_CALL); the result does not depend on
     it.  All cameras must share one image size (the result is one array); fields of view may differ."""
-    cams = list(cams)
+    cams, groups, H, W, window, h, w, device, G = _path_plan(cams, crop_ratio, frames_per_call, "render_frames")
     n = len(cams)
-    if n == 0:
-        raise ValueError("no cameras")
-    groups = frame_groups(cams, FRAMES_PER_CALL if frames_per_call is None else frames_per_call)
-    H, W = int(cams[0].image_height), int(cams[0].image_width)
-    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
-        raise ValueError("render_frames returns one array: the cameras must share one image size")
-    window = center_crop_window(H, W, crop_ratio)
-    h, w = window[1] - window[0], window[3] - window[2]
-    if h < 1 or w < 1:
-        raise ValueError(f"crop_ratio {crop_ratio} leaves no pixel of a {W} x {H} image")
-    device = cams[0].world_view_transform.device
-    if device.type != "cuda":
-        raise RuntimeError("render_frames needs cameras and a cloud on a HIP device (no CPU fallback)")
-    G = max(e - b for b, e in groups)
     frames = np.empty((n, h, w, 3), dtype=np.uint8)
     ring = _HostRing((G, h, w, 3), frames)
     depths = torch.empty((n, H, W), dtype=torch.float32, device=device) if depth else None
@@ -400,135 +414,61 @@ def render_trainview(motion, cloud, bg, tone_mapping=None, gt_images=None, start
     return imgs, gts, both
 
 
+def _path_files(plan, cloud, bg, tone_mapping, encode, sink, capacity):
+    """A camera path made into files on the device, in three stages that overlap -- the three steps of a
+    device_files.Download, group g in slot g % 2: while group g is rendered, encoded and its sizes copied, the files of
+    group g - 2 go to the sink, then the bytes of group g - 1 are copied (that many bytes, not the slots).  plan: a
+    _path_plan; encode(uint8 frames [K,h,w,3] on the device) -> (files, sizes) on the device; sink(begin, blobs) takes the
+    finished files of the cameras begin, begin + 1, ...; capacity: the bytes a slot's host buffer starts with."""
+    slots = [device_files.Download(capacity) for _ in range(2)]
+    groups, last = plan.groups, len(plan.groups) - 1
+    for g, (b, e) in enumerate(groups):
+        color = render_group(plan.cams[b:e], cloud, bg)["render"]
+        slots[g % 2].read_sizes(*encode(frames_finish(color, tone_mapping, plan.window)))
+        if g >= 2:
+            sink(groups[g - 2][0], slots[g % 2].blobs())
+        if g >= 1:
+            slots[(g - 1) % 2].copy_bytes()
+    slots[last % 2].copy_bytes()
+    for g in range(max(last - 1, 0), last + 1):
+        sink(groups[g][0], slots[g % 2].blobs())
+
+
 @torch.no_grad()
 def write_frames_png(cams, cloud, bg, directory, tone_mapping=None, crop_ratio=1.0, frames_per_call=None):
     """render_frames' loop with the files made on the device: per group of cameras frames_finish -> png.encode, and what
-    crosses to the host is sizes[i] bytes of finished file per frame, through two pinned buffers, written as
-    directory/00000.png ... (the names write_frames gives).  Three stages overlap: while group g is rendered and encoded,
-    the bytes of group g - 1 are copied (its sizes are read first: that many bytes are copied, not the slot) and the files
-    of group g - 2 are written.  The pixels are render_frames'; returns the paths."""
+    crosses to the host is sizes[i] bytes of finished file per frame (_path_files), written as directory/00000.png ... (the
+    names write_frames gives).  The pixels are render_frames'; returns the paths."""
     from . import png
-    cams = list(cams)
-    if not cams:
-        raise ValueError("no cameras")
-    groups = frame_groups(cams, FRAMES_PER_CALL if frames_per_call is None else frames_per_call)
-    H, W = int(cams[0].image_height), int(cams[0].image_width)
-    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
-        raise ValueError("write_frames_png: the cameras must share one image size")
-    window = center_crop_window(H, W, crop_ratio)
-    h, w = window[1] - window[0], window[3] - window[2]
-    if h < 1 or w < 1:
-        raise ValueError(f"crop_ratio {crop_ratio} leaves no pixel of a {W} x {H} image")
-    if cams[0].world_view_transform.device.type != "cuda":
-        raise RuntimeError("write_frames_png needs cameras and a cloud on a HIP device (no CPU fallback)")
+    plan = _path_plan(cams, crop_ratio, frames_per_call, "write_frames_png")
     os.makedirs(directory, exist_ok=True)
-    G = max(e - b for b, e in groups)
-    stride = (png.bound(w, h, 3) + 15) // 16 * 16
-    pinned = [torch.empty((G, stride), dtype=torch.uint8).pin_memory() for _ in range(2)]
-    pinned_sizes = [torch.empty(G, dtype=torch.int64).pin_memory() for _ in range(2)]
-    paths = []
+    paths = [os.path.join(directory, f"{i:05d}.png") for i in range(len(plan.cams))]
 
-    def copy_bytes(job):        # stage 2: the sizes are on the host; enqueue a copy of that many bytes per file
-        job["sized"].synchronize()
-        job["sizes"] = pinned_sizes[job["slot"]][:job["count"]].tolist()
-        for k, size in enumerate(job["sizes"]):
-            pinned[job["slot"]][k, :size].copy_(job["files"][k, :size], non_blocking=True)
-        job["copied"] = torch.cuda.Event()
-        job["copied"].record()
+    def sink(begin, blobs):
+        for path, data in zip(paths[begin:], blobs):
+            with open(path, "wb") as f:
+                f.write(data)
 
-    def write(job):             # stage 3
-        job["copied"].synchronize()
-        for k, size in enumerate(job["sizes"]):
-            paths.append(os.path.join(directory, f"{job['begin'] + k:05d}.png"))
-            with open(paths[-1], "wb") as f:
-                f.write(pinned[job["slot"]][k, :size].numpy().tobytes())
-
-    jobs = []
-    for g, (b, e) in enumerate(groups):
-        files, sizes = png.encode(frames_finish(render_group(cams[b:e], cloud, bg)["render"], tone_mapping, window))
-        job = {"slot": g % 2, "begin": b, "count": e - b, "files": files, "sized": torch.cuda.Event()}
-        pinned_sizes[job["slot"]][:e - b].copy_(sizes.view(torch.int64), non_blocking=True)
-        job["sized"].record()
-        jobs.append(job)
-        if g >= 2:
-            write(jobs[g - 2])
-            jobs[g - 2] = None
-        if g >= 1:
-            copy_bytes(jobs[g - 1])
-    for job in jobs[-2:]:
-        if job is not None and "copied" not in job:
-            copy_bytes(job)
-    for job in jobs[-2:]:
-        if job is not None:
-            write(job)
+    # (a host buffer of the largest group's bound never grows)
+    _path_files(plan, cloud, bg, tone_mapping, png.encode, sink, plan.G * png.bound(plan.w, plan.h, 3))
     return paths
 
 
 @torch.no_grad()
 def write_frames_video(cams, cloud, bg, path, fps, tone_mapping=None, crop_ratio=1.0, frames_per_call=None, quality=90,
                        subsampling="4:2:0"):
-    """write_frames_png's three-stage loop with the frames made into JPEG files on the device (deblurgs_amd/jpeg.py) and
-    appended to ONE Motion-JPEG AVI (deblurgs_amd/video.py): while group g is rendered and encoded, the bytes of group g - 1
-    are copied (sizes first: that many bytes, not the slot) and the frames of group g - 2 are appended to the file.  The
-    frames are jpeg.to_bytes(render_frames(...)) byte for byte; returns the path."""
+    """The same loop with the frames made into JPEG files on the device (deblurgs_amd/jpeg.py) and appended to ONE
+    Motion-JPEG AVI (deblurgs_amd/video.py).  The frames are jpeg.to_bytes(render_frames(...)) byte for byte; returns the
+    path."""
     from . import jpeg, video
-    cams = list(cams)
-    if not cams:
-        raise ValueError("no cameras")
-    groups = frame_groups(cams, FRAMES_PER_CALL if frames_per_call is None else frames_per_call)
-    H, W = int(cams[0].image_height), int(cams[0].image_width)
-    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
-        raise ValueError("write_frames_video: the cameras must share one image size")
-    window = center_crop_window(H, W, crop_ratio)
-    h, w = window[1] - window[0], window[3] - window[2]
-    if h < 1 or w < 1:
-        raise ValueError(f"crop_ratio {crop_ratio} leaves no pixel of a {W} x {H} image")
-    if cams[0].world_view_transform.device.type != "cuda":
-        raise RuntimeError("write_frames_video needs cameras and a cloud on a HIP device (no CPU fallback)")
-    G = max(e - b for b, e in groups)
-    # (the bound is the worst case of noise at quality 100; the pinned buffers grow to what the frames really take)
-    pinned = [torch.empty(1 << 16, dtype=torch.uint8).pin_memory() for _ in range(2)]
-    pinned_sizes = [torch.empty(G, dtype=torch.int64).pin_memory() for _ in range(2)]
-
-    def copy_bytes(job):        # stage 2: the sizes are on the host; enqueue a copy of that many bytes per file
-        job["sized"].synchronize()
-        job["sizes"] = pinned_sizes[job["slot"]][:job["count"]].tolist()
-        if pinned[job["slot"]].numel() < sum(job["sizes"]):
-            pinned[job["slot"]] = torch.empty(2 * sum(job["sizes"]), dtype=torch.uint8).pin_memory()
-        at = 0
-        for k, size in enumerate(job["sizes"]):
-            pinned[job["slot"]][at:at + size].copy_(job["files"][k, :size], non_blocking=True)
-            at += size
-        job["copied"] = torch.cuda.Event()
-        job["copied"].record()
-
+    plan = _path_plan(cams, crop_ratio, frames_per_call, "write_frames_video")
     with video.MjpegAviWriter(path, fps, quality, subsampling) as out:
-        def write(job):         # stage 3
-            job["copied"].synchronize()
-            host, at = pinned[job["slot"]].numpy(), 0
-            for size in job["sizes"]:
-                out._add(host[at:at + size].tobytes(), (w, h))
-                at += size
+        def sink(begin, blobs):
+            for data in blobs:
+                out.add(data, (plan.w, plan.h))
 
-        jobs = []
-        for g, (b, e) in enumerate(groups):
-            files, sizes = jpeg.encode(frames_finish(render_group(cams[b:e], cloud, bg)["render"], tone_mapping, window),
-                                       quality, subsampling)
-            job = {"slot": g % 2, "count": e - b, "files": files, "sized": torch.cuda.Event()}
-            pinned_sizes[job["slot"]][:e - b].copy_(sizes.view(torch.int64), non_blocking=True)
-            job["sized"].record()
-            jobs.append(job)
-            if g >= 2:
-                write(jobs[g - 2])
-                jobs[g - 2] = None
-            if g >= 1:
-                copy_bytes(jobs[g - 1])
-        for job in jobs[-2:]:
-            if job is not None and "copied" not in job:
-                copy_bytes(job)
-        for job in jobs[-2:]:
-            if job is not None:
-                write(job)
+        _path_files(plan, cloud, bg, tone_mapping, lambda frames: jpeg.encode(frames, quality, subsampling), sink,
+                    video.HOST_BYTES)
     return path
 
 

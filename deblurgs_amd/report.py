@@ -238,7 +238,7 @@ def evaluate_names(i):
     return f"{i:03d}_gt.png", f"{i:03d}_render.png", f"{i:03d}_error.png"
 
 
-def _no_writer_with_device_png(writer, device_png):
+def no_writer_with_device_png(writer, device_png):
     if device_png and writer is not None:
         raise ValueError("device_png writes the files itself: it cannot be combined with a writer")
 
@@ -255,7 +255,7 @@ def write_view_report(directory, i, image, gt, writer=None, device_png=False):
     unclamped render the metrics were taken of (so the bytes and the error are those of the reference's torch
     expression, no second tone mapping), gt [3,H,W].  device_png=True: the three images become files on the device (one
     n = 3 png.encode call) instead of crossing to PIL; same names, same pixels."""
-    _no_writer_with_device_png(writer, device_png)
+    no_writer_with_device_png(writer, device_png)
     render_u8, gt_u8, error_u8 = view_report(image[None], gt[None], "identity")
     if device_png:
         return write_device_png(directory, evaluate_names(i), torch.stack([gt_u8[0], render_u8[0], error_u8[0]]))
@@ -288,7 +288,7 @@ def traj_render(motion, cloud, model_path, iteration, tone_mapping=None, num_vis
     as the reference makes them, each with its own draw.  One background is drawn per view (background None: torch.rand(3))
     and used for both; the reference draws one per query().  device_png=True: the n + 3 images of a view are compressed
     on the device in one png.encode call instead of by PIL on the host (same names, same pixels; not with a writer)."""
-    _no_writer_with_device_png(writer, device_png)
+    no_writer_with_device_png(writer, device_png)
     device = cloud._xyz.device
     if device.type != "cuda":
         raise RuntimeError("traj_render needs a motion module and a cloud on a HIP device (no CPU fallback)")

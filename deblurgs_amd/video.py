@@ -1,9 +1,11 @@
 """Videos of device frames: a Motion-JPEG AVI whose frames are the .jpg files dgs_jpeg_encode makes (deblurgs_amd/jpeg.py).
 
     MjpegAviWriter(path, fps, quality, subsampling)   append(frames): a device uint8 [n,h,w,3] is encoded on the device and
-                               sizes[i] bytes per frame cross to the host through a pinned buffer; bytes (or a list of bytes)
-                               are taken as finished JPEG files, so the container needs no GPU.  close() writes the index and
-                               the header counts.  A context manager.
+                               sizes[i] bytes per frame cross to the host through the writer's pinned buffer (one
+                               device_files.Download, its three steps back to back); bytes (or a list of bytes) are taken
+                               as finished JPEG files, so the container needs no GPU.  add(data, (w, h)) takes one finished
+                               file whose size the caller knows (render_path.write_frames_video).  close() writes the index
+                               and the header counts.  A context manager.
     write_video(frames, path, fps, ...)   the one-shot form for a device tensor.
     make_video(imgs, path, fps=32)        the reference's make_video (utils/export_utils.py:153): numpy arrays, lists of
                                frames or host tensors are uploaded in groups; device tensors are taken as they are.  It fits
@@ -22,12 +24,14 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import jpeg
+from . import device_files, jpeg
 
 MAX_FILE_BYTES = 1 << 31            # RIFF sizes are 32-bit and players treat them as signed
 HEADER_BYTES = 224                  # everything before the first 00dc chunk
 MOVI_AT = 220                       # offset of the 'movi' fourcc: index offsets count from here
 UPLOAD_GROUP = 8                    # frames make_video uploads per encode call
+HOST_BYTES = 1 << 16                # what a pinned host buffer for JPEG files starts with (jpeg.bound is the worst case of
+                                    # noise at quality 100; the buffer doubles to what the frames really take)
 AVIF_HASINDEX, AVIIF_KEYFRAME = 0x10, 0x10
 
 
@@ -73,7 +77,7 @@ class MjpegAviWriter:
         self.path = path
         self.size = None                    # (w, h) of the first frame
         self.index = []                     # (offset from the 'movi' fourcc, size) per frame
-        self._pinned = None
+        self._download = None               # device_files.Download, made by the first device tensor
         self._f = open(path, "wb")
         self._f.write(bytes(HEADER_BYTES))
         self._at = HEADER_BYTES
@@ -89,8 +93,8 @@ class MjpegAviWriter:
     def n_frames(self):
         return len(self.index)
 
-    def _add(self, data, size=None):
-        """One finished JPEG file as a 00dc chunk."""
+    def add(self, data, size=None):
+        """One finished JPEG file as a 00dc chunk.  size: its (w, h) where the caller knows it (else read from its SOF0)."""
         if self._f is None:
             raise ValueError("the writer is closed")
         size = jpeg_size(data) if size is None else size
@@ -109,10 +113,10 @@ class MjpegAviWriter:
     def append(self, frames):
         """frames: a uint8 [n,h,w,3] tensor on a HIP device (encoded there), or finished JPEG bytes / a list of them."""
         if isinstance(frames, (bytes, bytearray, memoryview)):
-            return self._add(bytes(frames))
+            return self.add(bytes(frames))
         if isinstance(frames, (list, tuple)) and all(isinstance(f, (bytes, bytearray, memoryview)) for f in frames):
             for f in frames:
-                self._add(bytes(f))
+                self.add(bytes(f))
             return None
         import torch
         if not isinstance(frames, torch.Tensor):
@@ -121,21 +125,12 @@ class MjpegAviWriter:
             raise RuntimeError("MjpegAviWriter.append needs a tensor on a HIP device (no CPU fallback)")
         if frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError("MjpegAviWriter.append takes a uint8 [n,h,w,3] tensor")
-        files, sizes = jpeg.encode(frames, self.quality, self.subsampling)
-        host_sizes = sizes.view(torch.int64).cpu().tolist()
-        total = sum(host_sizes)
-        if self._pinned is None or self._pinned.numel() < total:
-            self._pinned = torch.empty(max(total, 1 << 16), dtype=torch.uint8).pin_memory()
-        at = 0
-        for i, s in enumerate(host_sizes):
-            self._pinned[at:at + s].copy_(files[i, :s], non_blocking=True)
-            at += s
-        torch.cuda.current_stream(frames.device).synchronize()
-        host, at = self._pinned.numpy(), 0
-        size = (int(frames.shape[2]), int(frames.shape[1]))
-        for s in host_sizes:
-            self._add(host[at:at + s].tobytes(), size)
-            at += s
+        if self._download is None:
+            self._download = device_files.Download(HOST_BYTES)
+        self._download.read_sizes(*jpeg.encode(frames, self.quality, self.subsampling))
+        self._download.copy_bytes()
+        for data in self._download.blobs():
+            self.add(data, (int(frames.shape[2]), int(frames.shape[1])))
         return None
 
     def close(self):

@@ -181,6 +181,25 @@ def test_python_front_end(gpu, tmp_path):
     assert png.encode(dev[:0])[1].numel() == 0
 
 
+def test_download_of_a_strided_files_view(gpu):
+    """device_files.download alone: files= is a view into a wider tensor (row stride > width, 5 bytes in)."""
+    import torch
+    from deblurgs_amd import device_files, png
+    images = np.stack([pc.smooth_noise(33, 211, 3, seed=8), pc.random_image(33, 211, 3, seed=9),
+                       np.full((33, 211, 3), 7, np.uint8)])
+    need = png.bound(211, 33, 3)
+    wide = torch.full((3, need + 40), GUARD, dtype=torch.uint8, device="cuda")
+    files, sizes = png.encode(torch.from_numpy(images).cuda(), files=wide[:, 5:5 + need + 3])
+    assert files.stride(0) > files.shape[1]
+    blobs = device_files.download(files, sizes)
+    host, host_sizes = wide.cpu().numpy(), sizes.view(torch.int64).cpu().tolist()
+    assert blobs == [host[i, 5:5 + host_sizes[i]].tobytes() for i in range(3)]
+    assert blobs == png.to_bytes(torch.from_numpy(images).cuda())
+    for i in range(3):
+        _check(blobs[i], images[i])
+        assert (host[i, :5] == GUARD).all() and (host[i, 5 + host_sizes[i]:] == GUARD).all()
+
+
 # ------------------------------------------------------------------------------------------------- 8. end to end
 @pytest.fixture(scope="module")
 def small_scene(gpu):
@@ -258,3 +277,31 @@ def test_write_frames_png_equals_render_frames(small_scene, tmp_path):
     for i, p in enumerate(paths):
         pc.check_file(open(p, "rb").read(), want[i], png.chunks)
         assert np.array_equal(np.asarray(Image.open(p)), want[i])
+
+
+@pytest.fixture(scope="module")
+def seven_frames(small_scene):
+    """Seven cameras (the fixture's three, repeated) and the PNG files of their render_frames, made in one encode call."""
+    import torch
+    from deblurgs_amd import png, render_path
+    s = small_scene
+    cams = (s["cams"] * 3)[:7]
+    frames = render_path.render_frames(cams, s["cloud"], s["bg"], s["tm"], crop_ratio=0.9, frames_per_call=2)
+    want = png.to_bytes(torch.from_numpy(frames).cuda())
+    assert len(set(want)) == 3                           # (neighbours differ: a file in the wrong place shows)
+    return cams, want
+
+
+# groups 2, 2, 2, 1: every download slot is used again after its files were written; one camera and one group of seven:
+# nothing but the drain; groups 4, 3: no steady state
+@pytest.mark.parametrize("n,per_call", [(7, 2), (1, 2), (7, 7), (7, 4)])
+def test_write_frames_png_schedules(small_scene, seven_frames, tmp_path, n, per_call):
+    from deblurgs_amd import render_path
+    s = small_scene
+    cams, want = seven_frames
+    paths = render_path.write_frames_png(cams[:n], s["cloud"], s["bg"], str(tmp_path / "frames"), s["tm"], crop_ratio=0.9,
+                                         frames_per_call=per_call)
+    assert paths == [str(tmp_path / "frames" / f"{i:05d}.png") for i in range(n)]
+    assert sorted(os.listdir(tmp_path / "frames")) == [f"{i:05d}.png" for i in range(n)]
+    for i, p in enumerate(paths):
+        assert open(p, "rb").read() == want[i], i

@@ -216,6 +216,32 @@ def test_frame_groups():
     assert isinstance(rp.FRAMES_PER_CALL, int) and 1 <= rp.FRAMES_PER_CALL <= _lib.DGS_MAX_K
 
 
+def test_path_plan_refusals():
+    """What render_frames, write_frames_png and write_frames_video start from (_path_plan), named as the caller."""
+    import torch
+    from deblurgs_amd import render_path as rp
+    same = [_Cam(144, 96) for _ in range(5)]
+    for who in ("render_frames", "write_frames_png", "write_frames_video"):
+        with pytest.raises(ValueError, match="no cameras"):
+            rp._path_plan([], 1.0, None, who)
+        with pytest.raises(ValueError, match=f"{who}.*share one image size"):
+            rp._path_plan(same + [_Cam(96, 144)], 1.0, None, who)
+        with pytest.raises(ValueError, match="crop_ratio 0.0 leaves no pixel of a 144 x 96 image"):
+            rp._path_plan(same, 0.0, None, who)
+        with pytest.raises(ValueError, match="frames_per_call"):
+            rp._path_plan(same, 1.0, 0, who)
+        for cam in same:
+            cam.world_view_transform = torch.eye(4)
+        with pytest.raises(RuntimeError, match=f"{who} needs .* HIP device \\(no CPU fallback\\)"):
+            rp._path_plan(iter(same), 0.5, 2, who)
+    with pytest.raises(ValueError, match="no cameras"):
+        rp.render_frames([], None, None)
+    with pytest.raises(ValueError, match="no cameras"):
+        rp.write_frames_png([], None, None, os.devnull)
+    with pytest.raises(ValueError, match="no cameras"):
+        rp.write_frames_video([], None, None, os.devnull, 32)
+
+
 def test_write_frames(tmp_path):
     from deblurgs_amd import render_path as rp
     frames = (np.arange(2 * 5 * 7 * 3) % 256).astype(np.uint8).reshape(2, 5, 7, 3)
