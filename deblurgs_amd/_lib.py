@@ -276,6 +276,10 @@ EXPORTS = {
     "dgs_jpeg_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 5),
     "dgs_jpeg_encode": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_size_t, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3),
+    "dgs_draw_prims": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32] +
+                       [ctypes.c_void_p] * 2),
+    "dgs_cone_segments": (ctypes.c_int, [ctypes.c_int32] + [ctypes.c_void_p] * 2 + [ctypes.c_double] * 3 +
+                          [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 3),
     "dgs_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "dgs_profile_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "dgs_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),

@@ -48,6 +48,8 @@ SOURCES = {
     "png.hip": [],
     # JPEG colour conversion, transform, quantiser and Huffman coding: integers only
     "jpeg.hip": [],
+    # lines and discs: integers only; the camera cones restate numpy's double arithmetic one rounding per statement
+    "draw.hip": ["-ffp-contract=off"],
 }
 # (no float atomics anywhere in the library: every reduction has a fixed order or is an integer sum)
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -21,8 +21,9 @@ installed) and pinned by tests/golden/report_golden.npz.  PNG files are written 
 .npy; every writer argument is a callable writer(path, array) that takes the place of the file.  device_png=True
 (write_view_report, traj_render, evaluation.evaluate) compresses the files on the device instead (deblurgs_amd/png.py).
 
-Out of scope: colorize with a mask or a colour bar (cv2, a matplotlib canvas), camera-cone drawings, alignment plots,
-videos.  (LPIPS, the third number of evaluate(), is deblurgs_amd/lpips.py: evaluate(..., lpips=weights).)
+Out of scope: colorize with a mask or a colour bar (cv2, a matplotlib canvas).  (The camera-cone drawings, the alignment
+plots and the visualiser's videos are deblurgs_amd/progress.py; LPIPS, the third number of evaluate(), is
+deblurgs_amd/lpips.py: evaluate(..., lpips=weights).)
 """
 import ctypes
 import os

@@ -980,6 +980,42 @@ int dgs_jpeg_encode(const uint8_t* images, int32_t n, int32_t w, int32_t h, int3
                     int32_t quality, int32_t subsampling, uint8_t* files, size_t file_stride, uint64_t* sizes, void* tmp,
                     dgs_stream_t stream);
 
+/* ---- the training-progress visualiser's drawings (additions to ABI 15) ----
+ * dgs_draw_prims: n records int32 [n,6] = (x0, y0, x1, y1, r, rgb), rgb = R | G << 8 | B << 16, painted into img, uint8
+ * [H,W,3] on the device, in painter's order: a covered pixel takes the colour of the HIGHEST-index record that covers it,
+ * every other byte of img is left as it was.
+ *   r == 0   a one-pixel line from (x0, y0) to (x1, y1).  dx = |x1 - x0|, dy = |y1 - y0|; the major axis is y if dy > dx,
+ *            else x; maj, min = the larger, the smaller of dx, dy.  Step i = 0 .. maj moves i pixels along the major axis
+ *            from the start point and floor((2 min i + maj - 1) / (2 maj)) along the minor one (0 for a single point): the
+ *            integer Bresenham walk with error term maj - 2 min, a tie staying with the start point -- so a line is not
+ *            the same set of pixels as its reverse.  The UNCLIPPED line is walked; pixels outside the image are dropped.
+ *   r > 0    the filled disc (x - x0)^2 + (y - y0)^2 <= r^2.  Needs x1 == x0, y1 == y0 and r <= 64: else skipped.
+ *   r < 0    skipped.  A record with a |coordinate| above 2^29 is skipped too (the 64-bit products above stay exact).
+ * owner: uint32 [H,W] scratch of the caller's; the call clears it itself (it may be passed dirty).  Three enqueues on the
+ * caller's stream: the clear; one wave per record raising owner[pixel] to index + 1 with an integer atomicMax, the step
+ * range clipped to the image before the loop (no lane loops more than max(W, H) / 64 + 1 times, wherever the endpoints lie);
+ * a pass that writes the owner's colour.  The maximum does not depend on arrival order: the bytes are a function of the
+ * arguments.  Nothing allocated, no host synchronisation, nothing kept between calls.  Refused before anything is enqueued:
+ * a NULL pointer, W or H below 1, W H >= 2^31, a negative n, a misaligned prims or owner.  n = 0 succeeds and touches
+ * nothing. */
+int dgs_draw_prims(uint8_t* img, int32_t W, int32_t H, const int32_t* prims, int32_t n, uint32_t* owner,
+                   dgs_stream_t stream);
+
+/* dgs_cone_segments: draw_cone_on_render_img (utils/visualization.py:156-185) for C cameras, one thread each, in double
+ * with the float inputs promoted.  view float [C,16] (row-major 4 x 4 world-view matrices: the upper 3 x 3 is the
+ * camera-to-world rotation), campos float [C,3], render_view / render_proj float [16] (the world-view and full projection
+ * matrices of the camera the image was rendered from), rgb int32 [C], prims_out int32 [C * 8, 6]: all on the device.  The
+ * five vertices (0,0,0), (tanx, tany, 1), (tanx, -tany, 1), (-tanx, -tany, 1), (-tanx, tany, 1) times scale, w = 1, go to
+ * the world by c2w^T and to ndc by render_proj (row vectors); pix = ((ndc.xy + 1) (W, H) - 1) / 2 truncated toward zero.
+ * Camera c writes the records 8 c .. 8 c + 7 = the segments (0,1) (0,2) (0,3) (0,4) (1,2) (2,3) (3,4) (4,1) with r = 0 and
+ * rgb[c].  All eight get r = -1 when z / w < 0.1 for any vertex of the camera-LOCAL cone taken through render_view (the
+ * reference's test as written); a segment with an endpoint that is not finite or beyond 2^29 gets r = -1 (the reference
+ * swallows cv2.line's exception).  One launch.  Refused before it: a NULL pointer, W or H below 1, C negative or above
+ * 2^24, a misaligned pointer.  C = 0 succeeds without a launch. */
+int dgs_cone_segments(int32_t C, const float* view, const float* campos, double tanx, double tany, double scale,
+                      const float* render_view, const float* render_proj, int32_t W, int32_t H, const int32_t* rgb,
+                      int32_t* prims_out, dgs_stream_t stream);
+
 /* The cloud's activations as the raw_params kernels evaluate them -- clamp(opacity, 0, 1), exp(scaling) + scale_lb,
  * rotation / max(|rotation|, 1e-12): the reference's get_opacity / get_scaling / get_rotation getters
  * (scene/gaussian_model.py:114-137, scene/gaussian_activation.py:29-52) on device, bit-identical to what
