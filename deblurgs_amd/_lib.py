@@ -108,6 +108,24 @@ class DgsLpipsSqueezeWeights(ctypes.Structure):
                 ("lin", ctypes.c_void_p * 7)]
 
 
+class DgsJpegHuff(ctypes.Structure):
+    _fields_ = [("look", ctypes.c_uint16 * 256), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18),
+                ("vals", ctypes.c_uint8 * 256)]
+
+
+class DgsJpegPlan(ctypes.Structure):
+    """The fixed head of a decode plan (include/dgs_hip.h); uint32 interval_at[n_intervals + 1] follows it."""
+    _fields_ = [("magic", ctypes.c_uint32), ("plan_bytes", ctypes.c_uint32), ("file_bytes", ctypes.c_uint32),
+                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("channels", ctypes.c_int32),
+                ("hs", ctypes.c_int32), ("vs", ctypes.c_int32), ("mcus_x", ctypes.c_int32), ("mcus_y", ctypes.c_int32),
+                ("restart_interval", ctypes.c_int32), ("n_intervals", ctypes.c_int32),
+                ("scan_begin", ctypes.c_uint32), ("scan_end", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2),
+                ("quant", (ctypes.c_uint8 * 64) * 3), ("huff", DgsJpegHuff * 6)]
+
+
+E_JPEG_UNSUPPORTED, E_JPEG_CORRUPT = -4, -5     # DGS_E_JPEG_*
+JPEG_STATUS = {1: "plan does not fit the call", 2: "invalid Huffman code", 3: "coefficient index past 63",
+               4: "DC category past 11", 5: "restart interval ran out of bytes"}      # DGS_JPEG_S_*
 ADAM_MAX_GROUPS = 16
 PNG_SEGMENT = 16384        # DGS_PNG_SEGMENT of include/dgs_hip.h (tests/test_png_host.py keeps the two in step)
 ABI_VERSION = 15           # DGS_ABI_VERSION of include/dgs_hip.h (tests/test_abi.py keeps the two in step)
@@ -276,6 +294,11 @@ EXPORTS = {
     "dgs_jpeg_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 5),
     "dgs_jpeg_encode": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_size_t, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3),
+    "dgs_jpeg_decode_plan_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "dgs_jpeg_decode_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
+    "dgs_jpeg_decode_tmp_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
+    "dgs_jpeg_decode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p] + [ctypes.c_int32] * 5 +
+                        [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3),
     "dgs_draw_prims": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32] +
                        [ctypes.c_void_p] * 2),
     "dgs_cone_segments": (ctypes.c_int, [ctypes.c_int32] + [ctypes.c_void_p] * 2 + [ctypes.c_double] * 3 +

@@ -48,6 +48,8 @@ SOURCES = {
     "png.hip": [],
     # JPEG colour conversion, transform, quantiser and Huffman coding: integers only
     "jpeg.hip": [],
+    # JPEG decoding: integers only; the transform's products of a malformed file may wrap, as libjpeg's do
+    "jpeg_decode.hip": ["-fwrapv"],
     # lines and discs: integers only; the camera cones restate numpy's double arithmetic one rounding per statement
     "draw.hip": ["-ffp-contract=off"],
 }
@@ -140,7 +142,8 @@ def asan_runtime():
 
 def build_sanitized(force=False, verbose=False):
     os.makedirs(SAN_OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "dgs_common.h"), os.path.join(HERE, "..", "include", "dgs_hip.h")]
+    headers = [os.path.join(CSRC, "dgs_common.h"), os.path.join(CSRC, "jpeg_decode_core.h"),
+               os.path.join(HERE, "..", "include", "dgs_hip.h")]
     hipcc = _hipcc()
     common = [f for f in COMMON if f != "-O3"] + SAN_FLAGS
     jobs, objs = [], []
@@ -170,7 +173,7 @@ def build_sanitized(force=False, verbose=False):
 
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "dgs_common.h"), HEADER]
+    headers = [os.path.join(CSRC, "dgs_common.h"), os.path.join(CSRC, "jpeg_decode_core.h"), HEADER]
     hipcc = _hipcc()
     bid = build_id()
     jobs = []

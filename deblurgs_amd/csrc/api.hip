@@ -287,6 +287,7 @@ struct StageTimer {
 // error reporting for the other translation units of the library (dgs_common.h)
 int dgs_fail_arg(const char* msg) { return fail(DGS_E_ARG, "%s", msg); }
 int dgs_fail_hip(hipError_t e, const char* where) { return fail_hip(e, where); }
+int dgs_fail_code(int code, const char* msg) { return fail(code, "%s", msg); }
 
 extern "C" {
 

@@ -165,6 +165,7 @@ __device__ __forceinline__ bool dgs_totals_publish(T a, T c, float* __restrict__
 // error reporting for every translation unit: set dgs_last_error's text (api.hip), return the code
 int dgs_fail_arg(const char* msg);
 int dgs_fail_hip(hipError_t e, const char* where);
+int dgs_fail_code(int code, const char* msg);   // (any DGS_E_* code)
 
 struct DgsView {  // per-launch scalars shared by the kernels
   int P, D, M, W, H, K;

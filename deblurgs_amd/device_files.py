@@ -1,6 +1,7 @@
 """Images in, files out: what the device encoders (deblurgs_amd/png.py, jpeg.py) and their callers share -- the tensor check
 (as_nhwc), the buffers around the one library call (encode), the way the files reach the host (Download: sizes first, then
-sizes[i] bytes of each file, packed end to end; download() for a single call) and write_files."""
+sizes[i] bytes of each file, packed end to end; download() for a single call) and write_files.  Files in: pack, the one
+pinned buffer jpeg.decode uploads."""
 import torch
 
 from . import _lib
@@ -44,6 +45,24 @@ def encode(images, need, tmp_bytes, files, call, what):
 
 def _pinned(n, dtype):
     return torch.empty(n, dtype=dtype, pin_memory=n > 0)
+
+
+def pack(chunks, reserve=0):
+    """Files on their way to the device (jpeg.decode): chunks [(uint8 numpy array, alignment)] laid end to end in ONE pinned
+    host buffer after `reserve` leading bytes of the caller's (an index of the offsets, say), each at a multiple of its
+    alignment, the gaps zero, the total rounded up to 16.  Returns (the host uint8 tensor, the offsets): one .to(device)
+    uploads everything."""
+    offsets, at = [], reserve
+    for data, align in chunks:
+        at = (at + align - 1) // align * align
+        offsets.append(at)
+        at += int(data.size)
+    host = _pinned((at + 15) // 16 * 16, torch.uint8)
+    view = host.numpy()
+    view[:] = 0
+    for (data, _), off in zip(chunks, offsets):
+        view[off:off + int(data.size)] = data
+    return host, offsets
 
 
 class Download:

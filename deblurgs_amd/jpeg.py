@@ -10,11 +10,27 @@
     segments(data)             a small HOST parser of a JPEG byte string: (marker, payload) per segment, the entropy-coded
                                bytes as the payload of the SOS entry's successor (tests, tools).
 
+and decoded there (dgs_jpeg_decode, deblurgs_amd/csrc/jpeg_decode.hip): baseline files -- SOF0, one scan, gray or 4:4:4 /
+4:2:2 / 4:2:0, with or without restart markers, any Huffman tables -- to Pillow's pixels, bit for bit.
+
+    probe(data)                what the decoder would do with a file, from its plan (host only): size, channels,
+                               subsampling, restart interval, intervals.  Raises Unsupported (a ValueError) with the reason
+                               for a file it does not take, ValueError for a corrupt one.
+    decode(files, device)      a list of bytes of one size -> uint8 [n,h,w,c] on the device: one upload of files and plans,
+                               one read of the per-file status.  A scan is decoded one lane per restart interval: a file
+                               without DRI on ONE lane.
+    read_files(paths)          decode of the files named.
+    plan(data)                 the plan itself (dgs_jpeg_decode_plan): scene.py makes it once per file and hands it to decode.
+
 Three channels are RGB, one is gray.  subsampling "4:4:4" or "4:2:0" (ignored for gray); quality 1..100 scales the Annex K
 tables the way libjpeg does.  Colour conversion, the 8 x 8 transform and the quantiser are integer arithmetic stated in
 include/dgs_hip.h: the bytes are a function of the pixels (tests/jpeg_cases.py restates them in numpy).  Opt-in: video.py
 wraps the files into a Motion-JPEG AVI, render_path.write_frames_video writes a camera path.
 """
+import ctypes
+
+import numpy as np
+
 from . import _lib, device_files
 
 SUBSAMPLING = {"4:4:4": 0, "4:2:0": 1}      # DGS_JPEG_444, DGS_JPEG_420
@@ -60,6 +76,115 @@ def to_bytes(images, quality=90, subsampling="4:2:0"):
 def write_files(images, paths, quality=90, subsampling="4:2:0"):
     """images [n,...] -> the n files named by paths.  Returns the paths."""
     return device_files.write_files(images, paths, lambda images: to_bytes(images, quality, subsampling))
+
+
+# ------------------------------------------------------------------------------------------------- decoding
+class Unsupported(ValueError):
+    """A valid JPEG of a kind the device decoder does not take (progressive, CMYK, ...): hand it to a host reader."""
+
+
+def plan(data):
+    """The decode plan of one file (dgs_jpeg_decode_plan, on the host): a uint8 numpy array that starts with a
+    _lib.DgsJpegPlan.  Raises Unsupported with the reason, ValueError for a stream that breaks the format."""
+    data = bytes(data)
+    L = _lib.lib()
+    need = ctypes.c_size_t()
+    rc = L.dgs_jpeg_decode_plan_bytes(data, len(data), ctypes.byref(need))
+    if rc == 0:
+        out = np.zeros(need.value // 8, dtype=np.uint64).view(np.uint8)      # (8-byte aligned)
+        rc = L.dgs_jpeg_decode_plan(data, len(data), out.ctypes.data, out.size)
+        if rc == 0:
+            return out
+    reason = L.dgs_last_error().decode("utf-8", "replace")
+    if rc == _lib.E_JPEG_UNSUPPORTED:
+        raise Unsupported(reason)
+    if rc == _lib.E_JPEG_CORRUPT:
+        raise ValueError(f"corrupt JPEG: {reason}")
+    raise RuntimeError(f"libdgs_hip dgs_jpeg_decode_plan failed (code {rc}): {reason}")
+
+
+def _head(plan_bytes):
+    return _lib.DgsJpegPlan.from_buffer_copy(plan_bytes[:ctypes.sizeof(_lib.DgsJpegPlan)].tobytes())
+
+
+def probe(data):
+    """What the device decoder would do with the file: a dict -- width, height, channels, subsampling ("gray", "4:4:4",
+    "4:2:2" or "4:2:0"), restart_interval (MCUs, 0 = none), intervals (the lanes its scan is decoded on).  No GPU needed.
+    Raises Unsupported (a ValueError) with the reason for a file the decoder does not take."""
+    p = _head(plan(data))
+    sub = "gray" if p.channels == 1 else {(1, 1): "4:4:4", (2, 1): "4:2:2", (2, 2): "4:2:0"}[p.hs, p.vs]
+    return {"width": p.w, "height": p.h, "channels": p.channels, "subsampling": sub, "restart_interval": p.restart_interval,
+            "intervals": p.n_intervals}
+
+
+def decode(files, device="cuda", out=None, plans=None):
+    """files: a list of JPEG byte strings of one size and channel count -> uint8 [n,h,w,c] on the device (c = 3: RGB, 1:
+    gray), Pillow's pixels.  The plans are made on the host, files and plans go up in ONE copy, the kernels run
+    (dgs_jpeg_decode) and the per-file status comes back in ONE read.  out: a uint8 [n,h,w,c] device tensor to write into;
+    plans: what plan() gave for each file, where the caller has them already.  Raises Unsupported / ValueError from the
+    parser (naming the file's index) and ValueError naming the files whose scans turned out malformed on the device."""
+    import torch
+    from .raster_call import _ptr, _stream
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("jpeg.decode needs a HIP device (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    files = [bytes(f) for f in files]
+    n = len(files)
+    if n == 0:
+        raise ValueError("jpeg.decode needs at least one file")
+    if plans is None:
+        plans = []
+        for i, f in enumerate(files):
+            try:
+                plans.append(plan(f))
+            except Unsupported as e:
+                raise Unsupported(f"file {i}: {e}") from None
+            except ValueError as e:
+                raise ValueError(f"file {i}: {e}") from None
+    heads = [_head(p) for p in plans]
+    w, h, c = heads[0].w, heads[0].h, heads[0].channels
+    for i, p in enumerate(heads):
+        if (p.w, p.h, p.channels) != (w, h, c):
+            raise ValueError(f"the files of one decode call share one size: file {i} is {p.w} x {p.h} x {p.channels}, "
+                             f"file 0 is {w} x {h} x {c}")
+    # one host buffer: the index (file offset, plan offset per image), the plans (8-byte aligned), the files (4-byte)
+    host, at = device_files.pack([(p, 8) for p in plans] + [(np.frombuffer(f, dtype=np.uint8), 4) for f in files],
+                                 reserve=16 * n)
+    host.numpy()[:16 * n] = np.array([at[n:], at[:n]], dtype=np.uint64).T.reshape(-1).view(np.uint8)
+    with torch.cuda.device(device):
+        dev = host.to(device, non_blocking=True)
+        if out is None:
+            out = torch.empty((n, h, w, c), dtype=torch.uint8, device=device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, c) or out.device != device or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 [{n},{h},{w},{c}] tensor on {device}")
+        L = _lib.lib()
+        stride = (h * w * c + 3) // 4 * 4           # (packed stores: every image starts on a dword)
+        if n > 1 and stride != h * w * c:
+            target = torch.empty((n, stride), dtype=torch.uint8, device=device)      # rows of a padded buffer, compacted below
+        else:
+            target = out
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        tmp = torch.empty(max(L.dgs_jpeg_decode_tmp_bytes(n, w, h, c), 16), dtype=torch.uint8, device=device)
+        _lib.check(L.dgs_jpeg_decode(_ptr(dev), dev.numel(), _ptr(dev), n, w, h, c, max(p.n_intervals for p in heads),
+                                     _ptr(target), stride, _ptr(status), _ptr(tmp), _stream(device)), "dgs_jpeg_decode")
+        if target is not out:
+            out.view(n, -1).copy_(target[:, :h * w * c])
+        bad = status.cpu().tolist()
+    if any(bad):
+        raise ValueError("corrupt JPEG scan: " + ", ".join(
+            f"file {i} ({_lib.JPEG_STATUS.get(s, s)})" for i, s in enumerate(bad) if s))
+    return out
+
+
+def read_files(paths, device="cuda"):
+    """The .jpg files named by paths (one size, one channel count) -> uint8 [n,h,w,c] on the device."""
+    blobs = []
+    for path in paths:
+        with open(path, "rb") as f:
+            blobs.append(f.read())
+    return decode(blobs, device)
 
 
 def segments(data):

@@ -519,43 +519,80 @@ def _find_image(path):
     raise FileNotFoundError(path)
 
 
-def _load_images(cams, resolution, reader, device, what):
+def _device_jpeg(path):
+    """(file bytes, decode plan) of a .jpg / .jpeg file that jpeg.decode takes as RGB, else None: progressive, CMYK, gray and
+    malformed files -- everything jpeg.plan refuses -- stay with the image reader, as every other format does."""
+    if os.path.splitext(path)[1].lower() not in (".jpg", ".jpeg"):
+        return None
+    from . import jpeg
+    with open(path, "rb") as f:
+        data = f.read()
+    try:
+        plan = jpeg.plan(data)
+    except ValueError:
+        return None
+    head = jpeg._head(plan)
+    return (data, plan, (head.h, head.w, 3)) if head.channels == 3 else None
+
+
+def _load_images(cams, resolution, reader, device, what, device_jpeg=False):
     """float32 [n,3,h,w] on the device: every image read, uploaded and resized in groups of at most UPLOAD_BUDGET_BYTES.
     A group holds images of one channel count; RGBA images are resized through premultiplied alpha (resize_rgba_images)
-    and their first three planes are the ground truth, as in loadCam."""
+    and their first three planes are the ground truth, as in loadCam.  device_jpeg: the .jpg / .jpeg files the device
+    decoder takes (_device_jpeg) go up as FILES and are decoded there (jpeg.decode), inside the same groups, into the
+    8-bit source the resize reads; every other file is read by `reader` as without it."""
     if not cams:
         return None
-    stack, size, src_shape, pending = None, None, None, []
+    stack, size, src_shape, pending, shapes = None, None, None, [], []
 
     def flush(first):
         if pending:
-            src = torch.from_numpy(np.stack(pending)).to(device)
+            files = [k for k, e in enumerate(pending) if not isinstance(e, np.ndarray)]
+            if not files:
+                src = torch.from_numpy(np.stack(pending)).to(device)
+            else:
+                from . import jpeg
+                host = [k for k in range(len(pending)) if k not in set(files)]
+                src = torch.empty((len(pending),) + tuple(shapes[0]), dtype=torch.uint8, device=device)
+                decoded = jpeg.decode([pending[k][0] for k in files], device, plans=[pending[k][1] for k in files],
+                                      out=None if host else src)
+                if host:
+                    src[files] = decoded
+                    src[host] = torch.from_numpy(np.stack([pending[k] for k in host])).to(device)
             if src.shape[3] == 4:
                 stack[first:first + len(pending)] = resize_rgba_images(src, size)[:, :3]
             else:
                 resize_images(src, size, out=stack[first:first + len(pending)])
             pending.clear()
+            shapes.clear()
 
     first = 0
     for i, cam in enumerate(cams):
-        img = np.asarray(reader(_find_image(cam.image_path)))
-        if img.dtype != np.uint8 or img.ndim not in (2, 3):
-            raise ValueError(f"{cam.image_path}: the image reader must return uint8 [H,W,C], got {img.dtype} {img.shape}")
-        if img.ndim == 2:
-            img = img[:, :, None]
-        if img.shape[2] not in (3, 4):
-            raise ValueError(f"{cam.image_path}: {what} images must be RGB (or RGBA), got {img.shape[2]} channel(s)")
+        path = _find_image(cam.image_path)
+        item = _device_jpeg(path) if device_jpeg else None
+        if item is None:
+            img = np.asarray(reader(path))
+            if img.dtype != np.uint8 or img.ndim not in (2, 3):
+                raise ValueError(f"{cam.image_path}: the image reader must return uint8 [H,W,C], got {img.dtype} {img.shape}")
+            if img.ndim == 2:
+                img = img[:, :, None]
+            if img.shape[2] not in (3, 4):
+                raise ValueError(f"{cam.image_path}: {what} images must be RGB (or RGBA), got {img.shape[2]} channel(s)")
+            shape, entry = img.shape, np.ascontiguousarray(img)
+        else:
+            shape, entry = item[2], item[:2]
         if src_shape is None:
-            src_shape = img.shape[:2]
-            size = training_resolution(img.shape[1], img.shape[0], resolution)
+            src_shape = shape[:2]
+            size = training_resolution(shape[1], shape[0], resolution)
             stack = torch.empty((len(cams), 3, size[1], size[0]), dtype=torch.float32, device=device)
-        elif img.shape[:2] != src_shape:
-            raise ValueError(f"{what} images must share one size: {cam.image_path} is {img.shape[:2]}, the first is {src_shape}")
-        if pending and pending[0].shape[2] != img.shape[2]:
+        elif shape[:2] != src_shape:
+            raise ValueError(f"{what} images must share one size: {cam.image_path} is {shape[:2]}, the first is {src_shape}")
+        if pending and shapes[0][2] != shape[2]:
             flush(first)
             first = i
-        pending.append(np.ascontiguousarray(img))
-        if len(pending) * img.size >= UPLOAD_BUDGET_BYTES:
+        pending.append(entry)
+        shapes.append(shape)
+        if len(pending) * shape[0] * shape[1] * shape[2] >= UPLOAD_BUDGET_BYTES:
             flush(first)
             first = i + 1
     flush(first)
@@ -564,7 +601,7 @@ def _load_images(cams, resolution, reader, device, what):
 
 def load_colmap_scene(source_path, images="images", resolution=-1, eval=False, llffhold=0, random_init=False,
                       num_initial_pcd=0, z_near=0.2, z_far=100.0, activation="relu", device="cuda", image_reader=None,
-                      num_random_points=100_000):
+                      num_random_points=100_000, device_jpeg=False):
     """readColmapSceneInfo + cameraList_from_camInfos for a COLMAP dataset directory: a SceneData.
     source_path/sparse/0 holds cameras, images and points3D (.bin, else .txt); source_path/<images> the pictures.
         resolution       loadCam's rule (training_resolution); the images are resized on the device
@@ -576,6 +613,9 @@ def load_colmap_scene(source_path, images="images", resolution=-1, eval=False, l
                          comes from the cameras alone.  Draws from numpy's global generator.
         activation       "relu" or "sigmoid": the colour activation the cloud is made for
         image_reader     path -> uint8 [H,W,C] (default: PIL, or .npy arrays where PIL is not importable)
+        device_jpeg      True: baseline .jpg / .jpeg files (jpeg.probe says which) are uploaded as files and decoded on the
+                         device (jpeg.decode: Pillow's pixels, bit for bit) on their way into the resize; every other file
+                         goes through image_reader as before.  Off by default.
     The training images must share one size and one set of intrinsics (CameraMotionModule has one RefCamera)."""
     from .motion import RefCamera
     _need_cuda(device, "load_colmap_scene")
@@ -601,8 +641,8 @@ def load_colmap_scene(source_path, images="images", resolution=-1, eval=False, l
         rgb = (shs * C0 if sigmoid else shs * C0 + 0.5)[:xyz.shape[0]] * 255   # SH2RGB, as storePly receives it
     points, colors = _ply_round_trip(xyz, rgb)
     radius = nerfpp_radius(camera_centers(train), None if random_init else points)
-    gt = _load_images(train, resolution, reader, device, "training")
-    tests = _load_images(test, resolution, reader, device, "test")
+    gt = _load_images(train, resolution, reader, device, "training", device_jpeg)
+    tests = _load_images(test, resolution, reader, device, "test", device_jpeg)
     h, w = int(gt.shape[2]), int(gt.shape[3])
     ref = RefCamera(w, h, first.FovX, first.FovY, device=device)
     return SceneData(ref_cam=ref, gt_images=gt, init_c2w=_c2w_of(train), image_names=[c.image_name for c in train],

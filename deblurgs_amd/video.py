@@ -11,6 +11,8 @@
                                frames or host tensors are uploaded in groups; device tensors are taken as they are.  It fits
                                the writer= parameter of render_path.render_spiral / render_trainview.
     parse_avi(data)            a small HOST parser: (header dict, [frame bytes]) (tests, tools).
+    read_frames(path_or_bytes, device)    the frames of a Motion-JPEG AVI as a device uint8 [n,h,w,3]: parse_avi, then
+                               jpeg.decode (one upload, the frames decoded on the device).
 
 The container is built on the host: it is 8 bytes per frame plus an index.  AVI 1.0: RIFF 'AVI ' { LIST 'hdrl' { avih,
 LIST 'strl' { strh (vids / MJPG, dwScale / dwRate = the frame rate as a reduced fraction), strf (BITMAPINFOHEADER, MJPG,
@@ -233,3 +235,18 @@ def parse_avi(data):
         if key not in header:
             raise ValueError(f"not a complete AVI: no {key}")
     return header, frames
+
+
+def read_frames(path_or_bytes, device="cuda"):
+    """The frames of a Motion-JPEG AVI -- a path, or the file's bytes -- as uint8 [n,h,w,3] on the device: parse_avi on the
+    host, then jpeg.decode of the frame files (Pillow's pixels of each).  Raises ValueError for a file without frames and
+    what parse_avi and jpeg.decode raise."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    _, frames = parse_avi(data)
+    if not frames:
+        raise ValueError("the AVI holds no frame")
+    return jpeg.decode(frames, device)

@@ -980,6 +980,105 @@ int dgs_jpeg_encode(const uint8_t* images, int32_t n, int32_t w, int32_t h, int3
                     int32_t quality, int32_t subsampling, uint8_t* files, size_t file_stride, uint64_t* sizes, void* tmp,
                     dgs_stream_t stream);
 
+/* ---- JPEG files decoded on the device (additions to ABI 15) ----
+ * The pixels are libjpeg's (Pillow's `np.asarray(Image.open(f))`), bit for bit, for the files below; all arithmetic is
+ * integer, all shifts arithmetic, everything fits int32.  tests/jpeg_decode_cases.py restates the rules in numpy.
+ *   1 entropy    T.81 Annex F baseline: canonical Huffman codes from the DHT counts (Annex C), EXTEND (F.12), ZRL (0xF0) and
+ *                EOB, coefficients de-zigzagged to natural order, one DC predictor per component, reset to 0 at every RSTm;
+ *                FF 00 is a stuffed FF; an RSTm marker ends an interval at a byte boundary
+ *   2 transform  libjpeg's jidctint ("islow"): coefficient times 8-bit table entry; with DESCALE(x, n) = (x + (1 << (n-1))) >> n
+ *                the 1-D routine below runs over the 8 columns with n = 11, then over the 8 rows of that result with n = 18;
+ *                then + 128, clamped to 0..255.  The routine, on i0..i7:
+ *                  z1 = (i2 + i6) 4433, t2 = z1 - i6 15137, t3 = z1 + i2 6270, t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13,
+ *                  t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+ *                  a = i7, b = i5, c = i3, d = i1, z1 = a + d, z2 = b + c, z3 = a + c, z4 = b + d, z5 = (z3 + z4) 9633,
+ *                  a *= 2446, b *= 16819, c *= 25172, d *= 12299, z1 *= -7373, z2 *= -20995, z3 = z3 (-16069) + z5,
+ *                  z4 = z4 (-3196) + z5, a += z1 + z3, b += z2 + z4, c += z2 + z3, d += z1 + z4;
+ *                  out0..7 = DESCALE of t10 + d, t11 + c, t12 + b, t13 + a, t13 - a, t12 - b, t11 - c, t10 - d
+ *   3 upsampling libjpeg's "fancy" upsampling.  A component's plane is dh x dw, dh = ceil(h V / Vmax), dw = ceil(w H / Hmax);
+ *                the padding of the transform beyond it is never read.  dw <= 2: every sample replicated, 2 x horizontally
+ *                (and 2 x vertically at 2 x 2).  Otherwise at 2 x 1 (4:2:2): out[2x] = (3 P[x] + P[x-1] + 1) >> 2,
+ *                out[2x+1] = (3 P[x] + P[x+1] + 2) >> 2, at the ends out[0] = P[0], out[2dw-1] = P[dw-1]; at 2 x 2 (4:2:0):
+ *                output row 2r takes the neighbour row max(r-1, 0), row 2r+1 the row min(r+1, dh-1), S[x] = 3 P[r][x] +
+ *                P[nbr][x], out[2x] = (3 S[x] + S[x-1] + 8) >> 4, out[2x+1] = (3 S[x] + S[x+1] + 7) >> 4, at the ends
+ *                out[0] = (4 S[0] + 8) >> 4, out[2dw-1] = (4 S[dw-1] + 7) >> 4.  Cropped to h x w.
+ *   4 colour     cb = Cb - 128, cr = Cr - 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768)
+ *                >> 16), B = Y + ((116130 cb + 32768) >> 16), each clamped to 0..255.  One component: the channel is Y.
+ * Files taken: SOF0, 8 bits, ONE interleaved scan, 8-bit quantisation tables, 1 component or 3 with luma sampling 1 x 1,
+ * 2 x 1 or 2 x 2 and chroma 1 x 1, with or without DRI, any valid DHT tables; APPn and COM are skipped.  Refused as
+ * DGS_E_JPEG_UNSUPPORTED, the reason in dgs_last_error(): SOF1, SOF2 and above, several scans, a 16-bit DQT, 4 components,
+ * other sampling factors, Adobe APP14 with transform 0, component ids 'R' 'G' 'B' (such files are not malformed: a caller
+ * hands them to a host reader).  DGS_E_JPEG_CORRUPT: a stream that breaks the format -- a segment length past the end, DHT
+ * counts that sum past 256 or make no prefix code, table ids out of range, references to tables that are not defined, a zero
+ * dimension, restart markers out of order or a count of them that disagrees with DRI and the MCU count, a missing EOI, a
+ * scan too short to hold a picture of the size the header claims.
+ *
+ * dgs_jpeg_decode_plan (HOST ONLY: no HIP call, nothing on the device is touched) parses one file of `size` bytes into
+ * `plan`, plan_bytes bytes of the caller's, 8-byte aligned: a DgsJpegPlan followed by uint32 interval_at[n_intervals + 1].
+ * Interval i is the bytes [interval_at[i], interval_at[i+1] - 2) of the file (the two bytes before the next interval are
+ * its RSTm marker, those after the last interval the marker that ends the scan); the parser walks the scan once for EOI
+ * and takes the offsets from that walk.  dgs_jpeg_decode_plan_bytes reads the headers only and gives the size to pass
+ * (DGS_E_CAPACITY for a smaller one); both return the same code for the same file.
+ *
+ * dgs_jpeg_decode (enqueue only: no allocation, no synchronisation, nothing kept between calls, capturable): n files and
+ * their plans, both inside ONE device buffer `blob` of blob_bytes bytes, 16-byte aligned: index (device uint64 [n,2],
+ * 8-byte aligned, anywhere) holds for image i the offset in blob of its file (a multiple of 4) and of its plan (a multiple
+ * of 8).  All n images are w x h x channels; tables, sampling and DRI are each plan's own.  Image i is written as h w
+ * channels contiguous bytes (interleaved RGB, or gray) at images + i image_stride; images is 4-byte aligned and
+ * image_stride a multiple of 4 (packed stores).  status (device int32 [n]) is 0 or a DGS_JPEG_S_* code; an image with a
+ * non-zero status is written as zeros.  max_intervals: the largest n_intervals of the n plans (the entropy grid).  tmp:
+ * dgs_jpeg_decode_tmp_bytes bytes, any alignment: int16 coefficients and 8-bit component planes of channels * (2 ceil(w /
+ * 16)) * (2 ceil(h / 16)) blocks per image.  Five enqueues: the clears of status and of the coefficients, then
+ *   entropy   one LANE per restart interval (a file without DRI is one interval: its scan is decoded by one lane), a wave
+ *             of 64 per block, the image's six Huffman tables (8-bit lookahead, maxcode / offset for longer codes) in LDS;
+ *             only non-zero coefficients are stored.  A lane stops with DGS_JPEG_S_BAD_CODE, _INDEX (a coefficient index
+ *             past 63), _DC_CATEGORY (past 11) or _OUT_OF_BYTES; it reads no byte outside its interval and writes no
+ *             coefficient outside the blocks of its MCUs, whatever the scan holds.
+ *   transform 8 lanes per block: rule 2, columns then rows, the exchange through LDS; 8-bit planes.
+ *   pixels    4 pixels per lane: rules 3 and 4, dword stores.
+ * The kernels check the plan against the call (DGS_JPEG_S_PLAN: another size or channel count, geometry or interval count
+ * that disagree, offsets outside blob): a plan that is not the parser's costs its image a status, never a stray access.
+ * Refused before anything is enqueued (DGS_E_ARG): channels other than 1 and 3, w or h outside 1..65535, a negative n, a
+ * NULL pointer, misaligned blob / index / images / status, an image_stride below h w channels or no multiple of 4,
+ * max_intervals below 1, more than 2^31 - 1 blocks in all.  n = 0 succeeds without a launch. */
+#define DGS_E_JPEG_UNSUPPORTED (-4) /* a valid file of a kind the device decoder does not take (text in dgs_last_error) */
+#define DGS_E_JPEG_CORRUPT (-5)     /* a stream that breaks the format */
+#define DGS_JPEG_S_OK 0
+#define DGS_JPEG_S_PLAN 1
+#define DGS_JPEG_S_BAD_CODE 2
+#define DGS_JPEG_S_INDEX 3
+#define DGS_JPEG_S_DC_CATEGORY 4
+#define DGS_JPEG_S_OUT_OF_BYTES 5
+#define DGS_JPEG_PLAN_MAGIC 0x4E4C504Au /* "JPLN" */
+#define DGS_JPEG_LOOK 8                 /* bits of the Huffman lookahead */
+typedef struct DgsJpegHuff {
+  uint16_t look[1 << DGS_JPEG_LOOK]; /* by the next 8 bits: code length << 8 | symbol; 0: the code is longer than 8 bits */
+  int32_t maxcode[18];               /* [l]: the largest code of length l, -1 where there is none (l = 1..16) */
+  int32_t valoff[18];                /* [l]: index into vals of the first code of length l, minus that code */
+  uint8_t vals[256];                 /* the symbols in code order */
+} DgsJpegHuff;
+typedef struct DgsJpegPlan {
+  uint32_t magic;
+  uint32_t plan_bytes; /* of this struct and the interval table after it, rounded up to 8 */
+  uint32_t file_bytes;
+  int32_t w, h, channels;
+  int32_t hs, vs;            /* the luma sampling factors: 1 x 1, 2 x 1 or 2 x 2 (chroma is 1 x 1) */
+  int32_t mcus_x, mcus_y;    /* ceil(w / 8 hs), ceil(h / 8 vs) */
+  int32_t restart_interval;  /* DRI: MCUs per interval, 0 = none */
+  int32_t n_intervals;       /* ceil(mcus_x mcus_y / restart_interval), 1 without DRI */
+  uint32_t scan_begin;       /* the first byte after SOS */
+  uint32_t scan_end;         /* the 0xFF of the marker that ends the scan */
+  uint32_t reserved[2];
+  uint8_t quant[3][64];      /* per component, natural order */
+  DgsJpegHuff huff[6];       /* DC of components 0..2, AC of components 0..2 */
+} DgsJpegPlan;
+int dgs_jpeg_decode_plan_bytes(const uint8_t* data, size_t size, size_t* plan_bytes);
+int dgs_jpeg_decode_plan(const uint8_t* data, size_t size, void* plan, size_t plan_bytes);
+size_t dgs_jpeg_decode_tmp_bytes(int32_t n, int32_t w, int32_t h, int32_t channels);
+int dgs_jpeg_decode(const uint8_t* blob, size_t blob_bytes, const uint64_t* index, int32_t n, int32_t w, int32_t h,
+                    int32_t channels, int32_t max_intervals, uint8_t* images, size_t image_stride, int32_t* status,
+                    void* tmp, dgs_stream_t stream);
+
 /* ---- the training-progress visualiser's drawings (additions to ABI 15) ----
  * dgs_draw_prims: n records int32 [n,6] = (x0, y0, x1, y1, r, rgb), rgb = R | G << 8 | B << 16, painted into img, uint8
  * [H,W,3] on the device, in painter's order: a covered pixel takes the colour of the HIGHEST-index record that covers it,
